@@ -3,8 +3,13 @@
 samples (BASELINE.json configs[1]; configs[3] when launched on N GPUs: the frame is split into
 N row bands, one per rank, and gathered to rank 0 over RCCL).
 
-Sub-records in the same JSON line (after the headline, same timing protocol: warm-up, barrier +
-synchronize on both sides, max over ranks):
+A plain run sets up, warms up, times the K steps and prints the headline record (with the
+rooflines read from the HIP events of the timed steps).  ``--dump-outputs DIR`` also writes what
+the last timed step returned on rank 0, the gathered (H*W, 5) float32 frame [rgb, depth, acc],
+as DIR/frame.npy (6.1 MB); the inputs are fixed, so two builds compare output for output.
+
+``--full`` adds the sub-records below and the CPU baseline to the same JSON line (after the
+headline, same timing protocol: warm-up, barrier + synchronize on both sides, max over ranks):
   "render_fp32"     the same C2 frame on the exact-fp32 MFMA MLP (NeRF(precision="fp32"); N = 1
                     only; min(K, 5) timed steps after 1 warm-up: 0.7 s per frame)
   "articulated"     config C3 -- NeRF_AE_Art 320x240 frame render (N = 1 only)
@@ -18,6 +23,7 @@ each with its own ms_per_step and roofline (MFMA fraction of the fine-level MLP 
 HBM byte fractions of the training kernels counting the stored activations).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--precision fp32] [--backend gloo]
+                    [--dump-outputs DIR] [--full [--no-extra] [--no-cpu-baseline]]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
 ``--gpus N`` (N > 1) without an external launcher spawns the N ranks itself, one process per
@@ -30,8 +36,8 @@ A step = generate the frame's rays, coarse sample, coarse MLP, the fused coarse 
 pdf resample (aon_composite_march), fine MLP, composite, gather.  value = 307,200 rays x steps / max-over-ranks wall time.  Rank 0 prints
 ONE JSON line.  Inputs: create_spheric_poses(4)[7] camera, fovy-35 focal, near 2 / far 6,
 random NeRF weights (aonerf.synthetic, PCG64 seed 0: the oracle's test weights bit for bit,
-tests/test_synthetic.py).  The CPU baseline is the torch restatement in oracle/ on a bounded
-ray sample (test infrastructure, never the measured path).
+tests/test_synthetic.py).  The CPU baseline (--full) is the torch restatement in oracle/ on a
+bounded ray sample (test infrastructure, never the measured path).
 """
 import argparse
 import json
@@ -77,14 +83,18 @@ def main():
     ap.add_argument("--steps", type=int, default=10)  # >= 10 timed, 3 warm-up
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--precision", default="f16x3", choices=sorted(PEAK_TFLOPS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the sub-records (fp32 / articulated renders, C5 training "
+                         "steps) and the CPU baseline with its parity check")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip that leg")
     ap.add_argument("--cpu-chunks", type=int, default=16,
                     help="3840-ray chunks in the CPU sample (SURVEY.md 8(d): 16)")
-    ap.add_argument("--no-extra", action="store_true", help="headline C2 render only")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the sub-records")
     ap.add_argument("--backend", default="nccl", choices=("nccl", "gloo"),
                     help="process-group backend for N > 1 (gloo: ranks may share one GPU)")
-    ap.add_argument("--dump-frame", default=None,
-                    help="rank 0 saves the gathered frame of the last timed step (.npy)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 saves what the last timed step returned, the gathered frame, as "
+                         "DIR/frame.npy (float32)")
     args = ap.parse_args()
 
     from aonerf import launch
@@ -120,8 +130,9 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = launch.max_over_ranks(time.perf_counter() - t0)
-    if rank == 0 and args.dump_frame:
-        np.save(args.dump_frame, frame.cpu().numpy())
+    if rank == 0 and args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "frame.npy"), frame.float().cpu().numpy())
 
     # per-launch kernel times from HIP events on the launch stream
     def avg_ms(key):
@@ -140,7 +151,7 @@ def main():
             print(f"[bench] {name}", file=sys.stderr, flush=True)
         extra[name] = fn(*a, **k)
 
-    if not args.no_extra:  # every rank takes part (the C5 step all-reduces over RCCL)
+    if args.full and not args.no_extra:  # every rank takes part (the C5 step all-reduces over RCCL)
         if world == 1:
             if args.precision != "fp32":
                 run("render_fp32", bench_render_fp32, args, c2w, focal)
@@ -216,7 +227,7 @@ def main():
                                  "launch_ms": march_ms, "algorithmic_bytes_per_launch": mb}
 
     out.update(extra)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(net, frame, c2w, focal, args.cpu_chunks)
     print(json.dumps(out), flush=True)
     if world > 1:

@@ -13,7 +13,7 @@
 #   composite  tools/prof_composite.py                        (per-ray kernels)
 #   gemm       tools/prof_gemm.py                             (weight-gradient GEMM)
 #   train      tools/prof_train_step.py                       (C5 step; --art, --precision ...)
-#   bench      bench.py --no-cpu-baseline                     (every bench record)
+#   bench      bench.py --full --no-cpu-baseline              (every bench record)
 #   bf16-sha   tools/diag/bf16_ab_outputs.py                  (sha of every bf16-step output)
 #   trainrec   tools/prof_train_records.py                    (C5 records + fine-level kernel ms)
 # env: ROUNDS (default 2), TOOL_ARGS (extra arguments), LIMIT (seconds per run, default 300).
@@ -27,7 +27,7 @@ case $TOOL in
   composite) CMD="tools/prof_composite.py" ;;
   gemm) CMD="tools/prof_gemm.py" ;;
   train) CMD="tools/prof_train_step.py" ;;
-  bench) CMD="bench.py --no-cpu-baseline" ;;
+  bench) CMD="bench.py --full --no-cpu-baseline" ;;
   bf16-sha) CMD="tools/diag/bf16_ab_outputs.py" ;;
   trainrec) CMD="tools/prof_train_records.py" ;;
   *) echo "unknown TOOL $TOOL"; exit 2 ;;

@@ -17,7 +17,7 @@ step() {  # step <name> <timeout> <cmd...>: run, log, stop the session on crash/
   return 0
 }
 [ "${SKIP_TESTS:-0}" = 1 ] || step pytest_gpu 1100 python -u -m pytest tests -m gpu -q -s -p no:cacheprovider --timeout 300 --timeout-method thread
-step bench 600 python bench.py "$@"
+step bench 600 python bench.py --full "$@"
 tail -1 "$OUT/bench.log" > "$OUT/bench.json"
 if [ "${EXTRA:-0}" = 1 ]; then
   step bench_art 600 python tools/bench_articulated.py
@@ -26,13 +26,13 @@ if [ "${EXTRA:-0}" = 1 ]; then
   tail -1 "$OUT/bench_train.log" > "$OUT/bench_train.json"
 fi
 [ "${SKIP_PROF:-0}" = 1 ] && exit 0
-step rocprof_kt 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -o run -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline "$@"
+step rocprof_kt 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -o run -- python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline "$@"
 if [ "${EXTRA:-0}" = 1 ]; then
   step rocprof_kt_art 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt_art" -o run -- python3 tools/bench_articulated.py --steps 3 --warmup 1
 fi
 [ "${SKIP_PMC:-0}" = 1 ] && exit 0
-step rocprof_fetch 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -o run -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline "$@"
+step rocprof_fetch 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -o run -- python3 bench.py --steps 1 --warmup 1 --full --no-cpu-baseline "$@"
 # effective clock under load (MI355X_MICROARCH.md 'DVFS give-back': GRBM_GUI_ACTIVE / 8 / wall)
-step rocprof_clock 600 rocprofv3 --pmc GRBM_GUI_ACTIVE --output-format csv -d "$OUT/pmc_clock" -o run -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline "$@"
-step rocprof_write 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write" -o run -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline "$@"
+step rocprof_clock 600 rocprofv3 --pmc GRBM_GUI_ACTIVE --output-format csv -d "$OUT/pmc_clock" -o run -- python3 bench.py --steps 1 --warmup 1 --full --no-cpu-baseline "$@"
+step rocprof_write 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write" -o run -- python3 bench.py --steps 1 --warmup 1 --full --no-cpu-baseline "$@"
 echo done

@@ -282,12 +282,12 @@ def test_bench_spawns_two_ranks_gloo(tmp_path):
     from aonerf.render import create_spheric_poses, render_frame, sapien_focal
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    dump = tmp_path / "frame.npy"
+    dump = tmp_path / "out"
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2",
                         "--backend", "gloo", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--dump-frame", str(dump)],
+                        "--full", "--no-cpu-baseline", "--dump-outputs", str(dump)],
                        env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
@@ -295,7 +295,9 @@ def test_bench_spawns_two_ranks_gloo(tmp_path):
     rec = json.loads(lines[0])
     assert rec["n_gpus"] == 2 and rec["backend"] == "gloo" and rec["steps"] == 2
     assert rec["config"]["parallelism"].startswith("row-band x2")
-    frame = np.load(dump)
+    assert os.listdir(dump) == ["frame.npy"]
+    frame = np.load(dump / "frame.npy")
+    assert frame.dtype == np.float32
     net = _net()
     ref = render_frame(net, create_spheric_poses(4.0)[7], 480, 640, sapien_focal(480)).cpu().numpy()
     np.testing.assert_array_equal(frame, ref)

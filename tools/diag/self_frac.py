@@ -35,7 +35,7 @@ def main():
     ap.add_argument("--ref-cache", default=None, help=".npz: load the fp32 oracle's outputs "
                     "from it if present, else compute and save them")
     ap.add_argument("--frame", action="append", default=[],
-                    help="a bench --dump-frame .npy (H*W x [rgb, depth, acc]) to compare too")
+                    help="a bench --dump-outputs frame.npy (H*W x [rgb, depth, acc]) to compare too")
     args = ap.parse_args()
     c2w = np.asarray(O.create_spheric_poses(4.0)[7], np.float32)
     focal = O.focal_from_fovy(H)

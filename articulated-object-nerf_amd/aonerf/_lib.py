@@ -203,6 +203,8 @@ _SIGNATURES = {
                                   vp, vp, vp, vp]),
     "aon_image_mse": (c_int, [vp, vp, c_i64, c_i64, vp, c_int, vp, vp, vp]),
     "aon_to8b": (c_int, [vp, c_i64, vp, vp]),
+    "aon_ssim_workspace_bytes": (c_size, [c_i64, c_i64, c_i64]),
+    "aon_image_ssim": (c_int, [vp, vp, c_i64, c_i64, c_i64, vp, vp, vp, c_size, vp]),
     "aon_gemm_workspace_bytes": (c_size, [ctypes.POINTER(AonGemmArgs)]),
     "aon_gemm": (c_int, [ctypes.POINTER(AonGemmArgs), vp, c_size, vp]),
     "aon_gemm_batch_workspace_bytes": (c_size, [ctypes.POINTER(AonGemmArgs), c_int]),
@@ -247,6 +249,13 @@ def lib():
     if _lib is None:
         _lib = _load(LIB_PATH)
     return _lib
+
+
+def ssim_tile():
+    """(rows, columns) of one workgroup's SSIM output tile: the library's aon_ssim_tile, the
+    constants its launch code sizes the grid with."""
+    th, tw = (c_int * 2).in_dll(lib(), "aon_ssim_tile")
+    return int(th), int(tw)
 
 
 def use_library(path):

@@ -9,7 +9,11 @@ models/utils.py:12-27, 62-73, 102-109, model.py:459-507),
   rank.
 * ``store_image`` (to8b on the device, aon_to8b; JPEG write with PIL on the host, as the
   reference) and ``write_stats`` (the same JSON).
-SSIM / LPIPS need piqa's pretrained networks, absent offline: not provided.
+* ``ssim_each`` / ``ssim`` / ``ssim_legacy`` / ``ssim_map``: piqa's SSIM with its defaults (a
+  closed-form windowed statistic, no learned parameters) from one aon_image_ssim launch for all
+  images, window sums in fp64; the dict layout of LitModel.ssim.  ``SSIM_TILE`` is the kernel's
+  output tile (rows, columns).
+LPIPS is not provided: it needs pretrained VGG weights, absent offline.
 """
 import json
 import os
@@ -84,6 +88,73 @@ def mse(image_pred, image_gt, valid_mask=None, reduction="mean"):
     return _image_mse([image_pred], [image_gt], masks=masks, clip=False)[0][0]
 
 
+def __getattr__(name):
+    # SSIM_TILE = (TH, TW): read from the library (its launch code's constants) on first use
+    if name == "SSIM_TILE":
+        return L.ssim_tile()
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+def _stack_hw(images):
+    imgs = [L.contig(i.float()) for i in images]
+    if not imgs:
+        raise ValueError("no images")
+    shape = tuple(imgs[0].shape)
+    if len(shape) != 3 or shape[2] != 3:
+        raise ValueError(f"images must be (h, w, 3), got {shape}")
+    if any(tuple(i.shape) != shape for i in imgs):
+        raise ValueError("all images of one call must have the same shape")
+    return torch.stack(imgs), shape[0], shape[1]
+
+
+def _image_ssim(preds, gts, want_map=False):
+    p, h, w = _stack_hw(preds)
+    g, hg, wg = _stack_hw(gts)
+    if (hg, wg) != (h, w) or p.shape[0] != g.shape[0]:
+        raise ValueError("preds and gts differ in shape")
+    if h < 11 or w < 11:
+        raise ValueError(f"SSIM's 11x11 window needs h, w >= 11, got {h}x{w}")
+    L.require_gpu(p, g)
+    n = p.shape[0]
+    out = torch.empty((n,), device=p.device)
+    ss_map = torch.empty((n, 3, h - 10, w - 10), device=p.device) if want_map else None
+    nbytes = L.lib().aon_ssim_workspace_bytes(n, h, w)
+    work = torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=p.device)
+    L.call("aon_image_ssim", L.ptr(p), L.ptr(g), n, h, w, L.ptr(out), L.ptr(ss_map), L.ptr(work),
+           nbytes, L.stream(p.device))
+    return out, ss_map
+
+
+@torch.no_grad()
+def ssim_each(preds, gts):
+    """interface.py:101-111: per-image SSIM (piqa.ssim.SSIM() defaults) of lists of (h, w, 3)
+    images, both sides clipped to [0, 1]; one launch for the whole list."""
+    return _image_ssim(preds, gts)[0]
+
+
+@torch.no_grad()
+def ssim(preds, gts, i_train=None, i_val=None, i_test=None):
+    """interface.py:141-155: {"name": "SSIM", "mean": m, "test": m}."""
+    m = ssim_each(preds, gts).mean().item()
+    return {"name": "SSIM", "mean": m, "test": m}
+
+
+_ssim_stats = ssim  # (test_epoch's `ssim` keyword shadows the function)
+
+
+@torch.no_grad()
+def ssim_legacy(pred, gt):
+    """interface.py:84-91: the SSIM of one (h, w, 3) pair as a 1-element tensor."""
+    return _image_ssim([pred], [gt])[0]
+
+
+@torch.no_grad()
+def ssim_map(pred, gt):
+    """The channel-wise SSIM map of one (h, w, 3) pair, (3, h-10, w-10): its mean is the
+    image's SSIM."""
+    return _image_ssim([pred], [gt], want_map=True)[1][0]
+
+
 def split_images(flat, image_sizes):
     """The reshape half of LitModel.alter_gather_cat (interface.py:40-51): a flat (sum h*w, C)
     tensor -> list of (h, w, C) / (h, w) images."""
@@ -123,12 +194,13 @@ def write_stats(fpath, *stats):
 
 
 @torch.no_grad()
-def test_epoch(model, dataset, out_dir=None, group=None):
+def test_epoch(model, dataset, out_dir=None, group=None, ssim=False):
     """LitNeRF's test loop + test_epoch_end (model.py:329-348, 459-507) over a SapienDataset
     test/val split: every image is rendered in row bands across the ranks of `group`
     (aonerf.parallel, one RCCL gather per image), then on rank 0: PSNR, object PSNR over the
     images' instance masks, optional image store + results.json.  Returns the stats dicts on
-    rank 0 (None elsewhere)."""
+    rank 0 (None elsewhere): (psnr, psnr_obj), or with ``ssim=True`` (psnr, psnr_obj, ssim) and
+    an "SSIM" entry in results.json."""
     import torch.distributed as dist
 
     from .parallel import render_frame_sharded
@@ -149,8 +221,10 @@ def test_epoch(model, dataset, out_dir=None, group=None):
     if rank != 0:
         return None
     stats = (psnr(rgbs, targets), psnr_obj(rgbs, targets, masks))
+    if ssim:
+        stats += (_ssim_stats(rgbs, targets),)
     if out_dir is not None:
         store_image(out_dir, rgbs, "image")
         write_stats(os.path.join(out_dir, "results.json"), stats[0],
-                    dict(stats[1], name="PSNR_obj"))
+                    dict(stats[1], name="PSNR_obj"), *stats[2:])
     return stats

@@ -26,7 +26,9 @@ typedef void* aon_stream_t; /* hipStream_t */
 
 #define AON_ABI_VERSION 13 /* 13: pos_enc's sin and the alpha exp correctly rounded, sigmoid as
                             * torch's CPU kernel forms it; the 32x32x16 precision of ABI 12
-                            * (value 3) withdrawn: measured slower */
+                            * (value 3) withdrawn: measured slower.
+                            * Added since, without a version change (purely additive):
+                            * aon_ssim_workspace_bytes, aon_image_ssim, aon_ssim_tile */
 
 /* Precision of the MLP GEMMs (see DESIGN.md "MLP precision modes"). */
 #define AON_PREC_FP32 0  /* exact fp32 MFMA (v_mfma_f32_16x16x4_f32) */
@@ -392,6 +394,27 @@ int aon_image_mse(const float* pred, const float* gt, int64_t n_images, int64_t 
 
 /* to8b (models/utils.py:12-13): out = uint8(255 * clip(x, 0, 1)) (truncating cast). */
 int aon_to8b(const float* x, int64_t n, uint8_t* out, aon_stream_t stream);
+
+/* SSIM of n_images image pairs ((n, H, W, 3) fp32, H, W >= 11), as LitModel.ssim_each forms it
+ * with piqa's SSIM defaults (models/interface.py:101-111): both sides clipped to [0, 1]; the
+ * 11-tap Gaussian window g[i] ~ exp(-(i-5)^2 / (2 1.5^2)) (sum 1), g x g applied without
+ * padding per channel; with mx = G*x, my = G*y, sxx = G*(x^2) - mx^2, syy = G*(y^2) - my^2,
+ * sxy = G*(x y) - mx my, c1 = 0.01^2, c2 = 0.03^2:
+ *   ss = (2 mx my + c1) / (mx^2 + my^2 + c1) * (2 sxy + c2) / (sxx + syy + c2);
+ * ssim[i] = mean of ss over the 3 channels and the (H-10)(W-10) window positions of image i.
+ * The window sums are evaluated in fp64 (an fp32 evaluation drifts by up to ~7e-5 on near-flat
+ * images, where E[x^2] - mx^2 cancels against c2: DESIGN.md "Metrics").  Deterministic: every
+ * aon_ssim_tile[0] x aon_ssim_tile[1] output tile leaves one fp64 partial sum in `work`, summed
+ * per image in tile order by a second kernel (no floating-point atomics).
+ * ss_map (may be NULL): the channel-wise map, (n, 3, H-10, W-10) fp32.
+ * work: aon_ssim_workspace_bytes(n_images, height, width) bytes, 8-byte aligned (0 from the
+ * query: invalid shape).  n_images == 0 returns 0 and launches nothing, whatever the pointers;
+ * n_images and the tile rows are grid dimensions: at most 65535 each. */
+extern const int aon_ssim_tile[2]; /* {rows, columns} of one workgroup's output tile */
+size_t aon_ssim_workspace_bytes(int64_t n_images, int64_t height, int64_t width);
+int aon_image_ssim(const float* pred, const float* gt, int64_t n_images, int64_t height,
+                   int64_t width, float* ssim, float* ss_map, void* work, size_t work_bytes,
+                   aon_stream_t stream);
 
 /* ---------------------------------------------------------------- training path */
 /* C (M x N) = epilogue(A (M x K) . B (K x N)): fp32 operands, fp16-MFMA hi/lo split

@@ -91,6 +91,41 @@ int main() {
   aon_adam_tensor t;
   std::memset(&t, 0, sizeof(t));
   expect_invalid(aon_adam_step(&t, 0, 1e-3, 0.9, 0.999, 1e-8, 1, nullptr), "adam count 0");
+  // aon_image_ssim: every refusal happens before the first launch; zero images is a no-op that
+  // does not look at the pointers
+  const size_t ssim_ws = aon_ssim_workspace_bytes(2, 24, 32);
+  expect_invalid(aon_image_ssim(nullptr, dummy, 2, 24, 32, dummy, nullptr, p, ssim_ws, nullptr),
+                 "image_ssim null pred");
+  expect_invalid(aon_image_ssim(dummy, nullptr, 2, 24, 32, dummy, nullptr, p, ssim_ws, nullptr),
+                 "image_ssim null gt");
+  expect_invalid(aon_image_ssim(dummy, dummy, 2, 24, 32, nullptr, nullptr, p, ssim_ws, nullptr),
+                 "image_ssim null ssim");
+  expect_invalid(aon_image_ssim(dummy, dummy, 2, 24, 32, dummy, nullptr, nullptr, ssim_ws, nullptr),
+                 "image_ssim null work");
+  expect_invalid(aon_image_ssim(dummy, dummy, 2, 10, 32, dummy, nullptr, p, ssim_ws, nullptr),
+                 "image_ssim height < 11");
+  expect_invalid(aon_image_ssim(dummy, dummy, 2, 24, 10, dummy, nullptr, p, ssim_ws, nullptr),
+                 "image_ssim width < 11");
+  expect_invalid(aon_image_ssim(dummy, dummy, -1, 24, 32, dummy, nullptr, p, ssim_ws, nullptr),
+                 "image_ssim negative count");
+  expect_invalid(aon_image_ssim(dummy, dummy, 2, -24, 32, dummy, nullptr, p, ssim_ws, nullptr),
+                 "image_ssim negative height");
+  expect_invalid(aon_image_ssim(dummy, dummy, 2, 24, 32, dummy, nullptr, p, ssim_ws - 1, nullptr),
+                 "image_ssim work_bytes too small");
+  expect_invalid(aon_image_ssim(dummy, dummy, 70000, 24, 32, dummy, nullptr, p, ~(size_t)0, nullptr),
+                 "image_ssim image count past the grid");
+  expect_invalid(aon_image_ssim(dummy, dummy, 1, 4000000, 32, dummy, nullptr, p, ~(size_t)0, nullptr),
+                 "image_ssim tile rows past the grid");
+  if (aon_image_ssim(nullptr, nullptr, 0, 24, 32, nullptr, nullptr, nullptr, 0, nullptr) != 0) {
+    std::printf("FAIL image_ssim zero images\n");
+    ++failures;
+  }
+  if (ssim_ws == 0 || aon_ssim_workspace_bytes(3, 24, 32) < ssim_ws ||
+      aon_ssim_workspace_bytes(0, 24, 32) == 0 || aon_ssim_workspace_bytes(2, 10, 32) != 0 ||
+      aon_ssim_workspace_bytes(-1, 24, 32) != 0 || aon_ssim_tile[0] < 1 || aon_ssim_tile[1] < 1) {
+    std::printf("FAIL ssim workspace query\n");
+    ++failures;
+  }
   // size queries: pure host arithmetic
   if (aon_mlp_packed_bytes(AON_PREC_F16X3) == 0 || aon_mlp_bwd_packed_bytes() == 0 ||
       aon_mlp_art_packed_bytes() == 0 || aon_colsum_workspace_bytes(1024, 256) == 0) {

@@ -21,6 +21,8 @@ PREC = {"fp32": 0, "f16x3": 1}
 PREC_F16X3_TRAIN = 1  # the training forwards' fp16x3 stream (aon_mlp_fwd_train)
 PREC_BF16 = 2  # the training step's bf16 mode (aon_mlp_fwd_train_bf16, aon_mlp_bwd_bf16)
 ACT_NONE, ACT_VANILLA, ACT_ARTIC = 0, 1, 2
+# opacity term of aon_loss_masked (AON_OPACITY_*)
+OPACITY = {None: 0, "mse": 1, "ce": 2, "autorf": 3}
 
 
 class AonMlpParams(ctypes.Structure):
@@ -215,6 +217,9 @@ _SIGNATURES = {
     "aon_mse": (c_int, [vp, vp, c_i64, c_float, vp, vp, vp]),
     "aon_loss_pair": (c_int, [vp, vp, vp, c_i64, vp, vp, vp, vp, vp]),
     "aon_loss_pair_bwd": (c_int, [vp, vp, c_i64, vp, vp, vp, vp, vp, vp]),
+    "aon_loss_masked": (c_int, [vp, vp, vp, vp, vp, vp, c_i64, vp, c_int, ctypes.c_double, c_int,
+                                vp, vp, vp, vp, vp, vp]),
+    "aon_loss_masked_bwd": (c_int, [vp, vp, vp, vp, c_i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "aon_colsum_workspace_bytes": (c_size, [c_i64, c_i64]),
     "aon_colsum": (c_int, [vp, c_i64, c_i64, c_i64, c_int, vp, vp, c_size, vp]),
     "aon_adam_step": (c_int, [ctypes.POINTER(AonAdamTensor), c_int, ctypes.c_double,

@@ -565,6 +565,94 @@ def loss_pair(pred0, pred1, target, reg=None):
     return LossPair.apply(pred0, pred1, target, reg)
 
 
+def _mask_u8(mask, n):
+    """The instance mask as (n,) uint8, non-zero = foreground (bool / uint8: no launch)."""
+    mask = mask.reshape(-1)
+    if mask.numel() != n:
+        raise ValueError(f"mask has {mask.numel()} entries for {n} rays")
+    if not mask.is_cuda:
+        raise ValueError("aonerf runs on the MI355X only: got a CPU mask")
+    if mask.dtype not in (torch.uint8, torch.bool):
+        mask = mask != 0
+    return L.contig(mask).view(torch.uint8)
+
+
+class MaskedLoss(torch.autograd.Function):
+    """The loss of a mask-supervised training step (model_autodecoder.py:423-454,
+    model_ae_art.py:380-408) in one aon_loss_masked launch: both levels' img2mse (over every ray,
+    or the foreground rays only), [+ reg], + one of the reference's opacity losses
+    (model_autodecoder.py:703-766) on the levels' acc against the instance mask.  Backward: one
+    aon_loss_masked_bwd launch for the rgb and acc gradients of both levels.  pred0 = pred1 =
+    target = None leaves the opacity term alone."""
+
+    @staticmethod
+    def forward(ctx, pred0, pred1, acc0, acc1, target, mask, reg, kind, lam, mask_rgb):
+        rgb = pred0 is not None
+        L.require_gpu(pred0, pred1, acc0, acc1, target)
+        ctx.acc_shapes = (acc0.shape, acc1.shape)
+        acc0, acc1 = L.contig(acc0).reshape(-1), L.contig(acc1).reshape(-1)
+        B = acc0.numel()
+        if acc1.numel() != B:
+            raise ValueError("MaskedLoss: the two levels' acc must have one shape")
+        if rgb:
+            pred0, pred1, target = L.contig(pred0), L.contig(pred1), L.contig(target)
+            if not (tuple(pred0.shape) == tuple(pred1.shape) == tuple(target.shape) == (B, 3)):
+                raise ValueError("MaskedLoss: predictions and target must be (B, 3) for B acc values")
+        mask = _mask_u8(mask, B)
+        dev = acc0.device
+        out = torch.empty((4,), device=dev)
+        g0 = g1 = a0 = a1 = None
+        if rgb:
+            g0, g1 = torch.empty_like(pred0), torch.empty_like(pred1)
+        if kind != 0:
+            a0, a1 = torch.empty_like(acc0), torch.empty_like(acc1)
+        L.call("aon_loss_masked", L.ptr(pred0), L.ptr(pred1), L.ptr(acc0), L.ptr(acc1),
+               L.ptr(target), L.ptr(mask), B, L.ptr(L.contig(reg)) if reg is not None else None,
+               kind, float(lam), int(bool(mask_rgb)), L.ptr(out), L.ptr(g0), L.ptr(g1), L.ptr(a0),
+               L.ptr(a1), L.stream(dev))
+        ctx.save_for_backward(g0, g1, a0, a1)
+        ctx.has_reg = reg is not None
+        ctx.set_materialize_grads(False)
+        psnr0, psnr1 = mse2psnr(out[1:3]).unbind(0)
+        loss, loss0, loss1, opacity = out.unbind(0)
+        ctx.mark_non_differentiable(psnr0, psnr1)
+        return loss, loss0, loss1, opacity, psnr0, psnr1
+
+    @staticmethod
+    def backward(ctx, g, g0, g1, gop, _p0, _p1):
+        grad0, grad1, gacc0, gacc1 = ctx.saved_tensors
+        none = (None,) * 10
+        if g is None and g0 is None and g1 is None and gop is None:
+            return none
+        d0 = d1 = e0 = e1 = None
+        if grad0 is not None:
+            d0, d1 = torch.empty_like(grad0), torch.empty_like(grad1)
+        if gacc0 is not None:
+            e0, e1 = torch.empty_like(gacc0), torch.empty_like(gacc1)
+        ref = gacc0 if gacc0 is not None else grad0
+        L.call("aon_loss_masked_bwd", L.ptr(grad0), L.ptr(grad1), L.ptr(gacc0), L.ptr(gacc1),
+               ref.shape[0],
+               *(L.ptr(L.contig(x)) if x is not None else None for x in (g, g0, g1, gop)),
+               L.ptr(d0), L.ptr(d1), L.ptr(e0), L.ptr(e1), L.stream(ref.device))
+        if e0 is not None:
+            e0, e1 = e0.view(ctx.acc_shapes[0]), e1.view(ctx.acc_shapes[1])
+        return (d0, d1, e0, e1, None, None, (g if ctx.has_reg else None), None, None, None)
+
+
+def masked_loss(pred0, pred1, acc0, acc1, target, mask, reg=None, *, opacity=None,
+                opacity_lambda=0.05, mask_rgb=False):
+    """(loss, loss0, loss1, opacity_term, psnr0, psnr1) of a mask-supervised training step
+    (MaskedLoss).  ``mask`` (B): non-zero = foreground; ``opacity``: None, "mse" (opacity_loss),
+    "ce" (opacity_loss_CE, weighted by ``opacity_lambda``: 0.05 in the reference's autodecoder,
+    0.5 in its model_ae_art) or "autorf" (opacity_loss_autorf as the reference writes it: its
+    fine foreground term reads the coarse opacity, model_autodecoder.py:761-763); ``mask_rgb``:
+    the colour losses over the foreground rays only (model_autodecoder.py:423-426)."""
+    if opacity not in L.OPACITY:
+        raise ValueError(f"opacity must be one of None, 'mse', 'ce', 'autorf'; got {opacity!r}")
+    return MaskedLoss.apply(pred0, pred1, acc0, acc1, target, mask, reg, L.OPACITY[opacity],
+                            opacity_lambda, mask_rgb)
+
+
 def training_step(model, batch, randomized, white_bkgd, near, far, *, u_coarse=None, u_fine=None,
                   timers=None):
     """LitNeRF.training_step (model.py:256-282): loss = mse(fine) + mse(coarse) and the psnrs.

@@ -35,7 +35,8 @@ from . import tiles
 from . import train as _train
 from .linalg import ACT_SCALE, GRAD_SCALE, W_SCALE, batched, gemm, small_batched
 from .numerics import ART_FORWARD, DEFAULT
-from .train import Adam, _amax_word, img2mse, learning_rate, loss_pair, mse2psnr, relu_masks  # noqa: F401 (shared)
+from .train import (Adam, _amax_word, img2mse, learning_rate, loss_pair, masked_loss,  # noqa: F401 (shared)
+                    mse2psnr, relu_masks)
 
 # parameter layout of one articulated NeRFMLP in ArtRenderLevel: 20 layers x (weight, bias)
 DEF0, DL, PTS0, DENS, BOT, VIEW0, RGB = 0, 4, 5, 13, 14, 15, 19
@@ -631,17 +632,59 @@ class LatentReg(torch.autograd.Function):
         return tuple(x * g for x in ctx.saved_tensors)
 
 
+def opacity_loss(rendered_results, instance_mask):
+    """LitNeRF_AutoDecoder.opacity_loss (model_autodecoder.py:703-717): sum over the two levels
+    of mean((clamp(acc, 0, 1) - mask)^2) -> a scalar under autograd (train.MaskedLoss, its
+    colour terms skipped).  ``rendered_results`` = the model's [(rgb, acc, depth)] per level."""
+    return masked_loss(None, None, rendered_results[0][1], rendered_results[1][1], None,
+                       instance_mask, opacity="mse")[3]
+
+
+def opacity_loss_CE(rendered_results, instance_mask, opacity_lambda=0.05):
+    """LitNeRF_AutoDecoder.opacity_loss_CE (model_autodecoder.py:719-736): opacity_lambda * the
+    levels' BCEWithLogitsLoss(acc, mask); the reference hard-codes opacity_lambda 0.05 here and
+    0.5 in model_ae_art.py:646-663."""
+    return masked_loss(None, None, rendered_results[0][1], rendered_results[1][1], None,
+                       instance_mask, opacity="ce", opacity_lambda=opacity_lambda)[3]
+
+
+def opacity_loss_autorf(rendered_results, instance_mask):
+    """LitNeRF_AutoDecoder.opacity_loss_autorf (model_autodecoder.py:738-766) as the reference
+    writes it: its fine foreground term reads the coarse opacity (:761-763), kept for parity."""
+    return masked_loss(None, None, rendered_results[0][1], rendered_results[1][1], None,
+                       instance_mask, opacity="autorf")[3]
+
+
 def training_step(model, code_library, batch, randomized, white_bkgd, near, far, *,
-                  u_coarse=None, u_fine=None, timers=None):
+                  u_coarse=None, u_fine=None, timers=None, opacity=None, opacity_lambda=0.05,
+                  mask_rgb=False):
     """LitNeRF_AutoDecoder.training_step (model_autodecoder.py:395-477) ->
     (loss, logs{loss0, loss1, reg, psnr0, psnr1}).  ``batch`` holds rays_o / rays_d / viewdirs /
     target (B, 3) and instance_id / articulation_id (1,) as the reference's loader gives them
     after its squeeze (model_autodecoder.py:396-399).  The kernels and precision are the model's
-    own (model.train_numerics)."""
+    own (model.train_numerics).
+
+    Mask supervision (the reference's commented-out terms, model_autodecoder.py:423-426 and
+    :441-454; live in model_ae_art.py:380-408): ``opacity`` = "mse" / "ce" / "autorf" adds
+    opacity_loss / opacity_loss_CE (weighted by ``opacity_lambda``) / opacity_loss_autorf of the
+    two levels' acc against batch["instance_mask"] (or batch["mask"]); ``mask_rgb`` takes the
+    colour losses over the foreground rays only.  The whole loss is then one aon_loss_masked
+    launch and ``logs`` gains ``opacity``.  With the defaults nothing changes."""
+    masked = opacity is not None or mask_rgb
+    if masked:
+        mask = batch.get("instance_mask", batch.get("mask"))
+        if mask is None:
+            raise ValueError("training_step: opacity / mask_rgb need batch['instance_mask'] "
+                             "(or batch['mask'])")
     latents = code_library(batch)
     ret = model(batch, randomized, white_bkgd, near, far, latents, u_coarse=u_coarse,
                 u_fine=u_fine, timers=timers)
     reg = LatentReg.apply(latents["density"], latents["color"], latents["articulation"])
+    if masked:
+        loss, loss0, loss1, op, psnr0, psnr1 = masked_loss(
+            ret[0][0], ret[1][0], ret[0][1], ret[1][1], batch["target"], mask, reg,
+            opacity=opacity, opacity_lambda=opacity_lambda, mask_rgb=mask_rgb)
+        return loss, dict(loss0=loss0, loss1=loss1, reg=reg, psnr0=psnr0, psnr1=psnr1, opacity=op)
     # loss1 + loss0 + reg and the psnrs in one launch (train.LossPair)
     loss, loss0, loss1, psnr0, psnr1 = loss_pair(ret[0][0], ret[1][0], batch["target"], reg)
     return loss, dict(loss0=loss0, loss1=loss1, reg=reg, psnr0=psnr0, psnr1=psnr1)

@@ -28,7 +28,8 @@ typedef void* aon_stream_t; /* hipStream_t */
                             * torch's CPU kernel forms it; the 32x32x16 precision of ABI 12
                             * (value 3) withdrawn: measured slower.
                             * Added since, without a version change (purely additive):
-                            * aon_ssim_workspace_bytes, aon_image_ssim, aon_ssim_tile */
+                            * aon_ssim_workspace_bytes, aon_image_ssim, aon_ssim_tile,
+                            * aon_loss_masked, aon_loss_masked_bwd */
 
 /* Precision of the MLP GEMMs (see DESIGN.md "MLP precision modes"). */
 #define AON_PREC_FP32 0  /* exact fp32 MFMA (v_mfma_f32_16x16x4_f32) */
@@ -557,6 +558,52 @@ int aon_loss_pair(const float* pred0, const float* pred1, const float* target, i
 int aon_loss_pair_bwd(const float* grad0, const float* grad1, int64_t n, const float* g_loss,
                       const float* g_loss0, const float* g_loss1, float* d0, float* d1,
                       aon_stream_t stream);
+
+/* The loss of a mask-supervised training step in one launch (one workgroup; no host read): the
+ * coarse (pred0, acc0) and fine (pred1, acc1) levels' colour (B,3) and accumulated opacity (B)
+ * against target (B,3) and the instance mask (B, uint8, non-zero = foreground).
+ *   Colour terms: mask_rgb == 0 -- img2mse over every ray, aon_loss_pair's arithmetic bit for
+ *   bit; mask_rgb != 0 -- img2mse(rgb[mask], target[mask]) (model_autodecoder.py:423-426,
+ *   model_ae_art.py:380): the mean over the 3 n_fg foreground values, gradient
+ *   2 (pred - target) / (3 n_fg) on foreground rows and 0 on background rows; with no foreground
+ *   ray the loss is NaN (0 / 0, torch's mean of an empty selection) and the gradients are 0.
+ *   pred0, pred1, target, grad_rgb0 and grad_rgb1 all NULL: the colour terms are skipped
+ *   (loss0 = loss1 = 0), which leaves the reference's stand-alone opacity losses.
+ *   Opacity term `kind`, formed in fp64 and rounded once:
+ *     AON_OPACITY_NONE    0; grad_acc0 / grad_acc1 may be NULL;
+ *     AON_OPACITY_MSE     opacity_loss (model_autodecoder.py:703-717, model_ae_art.py:630-644):
+ *                         sum over the levels of mean((clamp(acc, 0, 1) - m)^2); the gradient
+ *                         passes where 0 <= acc <= 1 (bounds included, torch's clamp backward);
+ *     AON_OPACITY_CE      opacity_loss_CE (model_autodecoder.py:719-736, model_ae_art.py:646-663):
+ *                         lambda * sum over the levels of mean(max(x,0) - x m + log1p(exp(-|x|)))
+ *                         (BCEWithLogitsLoss), gradient lambda (sigmoid(x) - m) / B; the
+ *                         reference's opacity_lambda is 0.05 (autodecoder) or 0.5 (model_ae_art);
+ *     AON_OPACITY_AUTORF  opacity_loss_autorf (model_autodecoder.py:738-766) AS THE REFERENCE
+ *                         WRITES IT, including what looks like a slip there: the fine level's
+ *                         foreground term reads the COARSE opacity (:761-763).  With bg_ratio =
+ *                         n_bg / B, fg_ratio = n_fg / B: bg_ratio (mean(acc0[bg]) + mean(acc1[bg]))
+ *                         when n_bg > 0, plus 2 fg_ratio mean(1 - acc0[fg]) when n_fg > 0;
+ *                         gradients bg_ratio / n_bg on both levels' background rays,
+ *                         -2 fg_ratio / n_fg on acc0's foreground rays, 0 on acc1's.
+ *   out[0] = loss1 + loss0 (+ *extra when extra != NULL: the latent regulariser) + opacity, added
+ *   in that order in fp32; out[1] = loss0, out[2] = loss1, out[3] = the opacity term.
+ *   `lambda` is a double (a Python float), used by AON_OPACITY_CE only. */
+#define AON_OPACITY_NONE 0
+#define AON_OPACITY_MSE 1
+#define AON_OPACITY_CE 2
+#define AON_OPACITY_AUTORF 3
+int aon_loss_masked(const float* pred0, const float* pred1, const float* acc0, const float* acc1,
+                    const float* target, const uint8_t* mask, int64_t B, const float* extra,
+                    int kind, double lambda, int mask_rgb, float* out, float* grad_rgb0,
+                    float* grad_rgb1, float* grad_acc0, float* grad_acc1, aon_stream_t stream);
+/* Its backward: d_rgb_i = grad_rgb_i * (g_loss + g_loss_i) over (B,3) and d_acc_i = grad_acc_i *
+ * (g_loss + g_opacity) over (B) for device scalars g_* (NULL = absent, taken as 0).  The four
+ * colour buffers, or the four opacity buffers, may be NULL together (that part is skipped). */
+int aon_loss_masked_bwd(const float* grad_rgb0, const float* grad_rgb1, const float* grad_acc0,
+                        const float* grad_acc1, int64_t B, const float* g_loss,
+                        const float* g_loss0, const float* g_loss1, const float* g_opacity,
+                        float* d_rgb0, float* d_rgb1, float* d_acc0, float* d_acc1,
+                        aon_stream_t stream);
 
 /* out[n] (+)= sum_m X[m*ldx + n] (bias gradients), deterministic order. */
 size_t aon_colsum_workspace_bytes(int64_t M, int64_t N);

@@ -126,6 +126,39 @@ int main() {
     std::printf("FAIL ssim workspace query\n");
     ++failures;
   }
+  // aon_loss_masked / aon_loss_masked_bwd: null pointers, B, kind and the buffers a kind needs
+  const uint8_t* mk = reinterpret_cast<const uint8_t*>(dummy);
+  expect_invalid(aon_loss_masked(dummy, dummy, nullptr, dummy, dummy, mk, 4, nullptr,
+                                 AON_OPACITY_MSE, 0.05, 0, dummy, dummy, dummy, dummy, dummy, nullptr),
+                 "loss_masked null acc0");
+  expect_invalid(aon_loss_masked(dummy, dummy, dummy, dummy, dummy, nullptr, 4, nullptr,
+                                 AON_OPACITY_MSE, 0.05, 0, dummy, dummy, dummy, dummy, dummy, nullptr),
+                 "loss_masked null mask");
+  expect_invalid(aon_loss_masked(dummy, nullptr, dummy, dummy, dummy, mk, 4, nullptr,
+                                 AON_OPACITY_MSE, 0.05, 0, dummy, dummy, dummy, dummy, dummy, nullptr),
+                 "loss_masked null pred1 alone");
+  expect_invalid(aon_loss_masked(dummy, dummy, dummy, dummy, dummy, mk, 0, nullptr,
+                                 AON_OPACITY_MSE, 0.05, 0, dummy, dummy, dummy, dummy, dummy, nullptr),
+                 "loss_masked B=0");
+  expect_invalid(aon_loss_masked(dummy, dummy, dummy, dummy, dummy, mk, 4, nullptr, 4, 0.05, 0,
+                                 dummy, dummy, dummy, dummy, dummy, nullptr),
+                 "loss_masked kind out of range");
+  expect_invalid(aon_loss_masked(dummy, dummy, dummy, dummy, dummy, mk, 4, nullptr,
+                                 AON_OPACITY_CE, 0.05, 0, dummy, dummy, dummy, nullptr, dummy, nullptr),
+                 "loss_masked CE without grad_acc0");
+  expect_invalid(aon_loss_masked(nullptr, nullptr, dummy, dummy, nullptr, mk, 4, nullptr,
+                                 AON_OPACITY_NONE, 0.05, 0, dummy, nullptr, nullptr, nullptr, nullptr,
+                                 nullptr),
+                 "loss_masked nothing to compute");
+  expect_invalid(aon_loss_masked_bwd(dummy, dummy, dummy, dummy, 4, dummy, nullptr, nullptr, nullptr,
+                                     dummy, nullptr, dummy, dummy, nullptr),
+                 "loss_masked_bwd null d_rgb1");
+  expect_invalid(aon_loss_masked_bwd(nullptr, nullptr, nullptr, nullptr, 4, dummy, nullptr, nullptr,
+                                     nullptr, nullptr, nullptr, nullptr, nullptr, nullptr),
+                 "loss_masked_bwd no buffers");
+  expect_invalid(aon_loss_masked_bwd(dummy, dummy, dummy, dummy, 0, dummy, nullptr, nullptr, nullptr,
+                                     dummy, dummy, dummy, dummy, nullptr),
+                 "loss_masked_bwd B=0");
   // size queries: pure host arithmetic
   if (aon_mlp_packed_bytes(AON_PREC_F16X3) == 0 || aon_mlp_bwd_packed_bytes() == 0 ||
       aon_mlp_art_packed_bytes() == 0 || aon_colsum_workspace_bytes(1024, 256) == 0) {

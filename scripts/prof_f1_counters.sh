@@ -11,5 +11,5 @@ timeout -k 10 300 python3 tools/prof_f1.py --reps 5 > "$OUT/timing.log" 2>&1 || 
 pass A SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT
 pass B SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_IDX_ACTIVE SQ_VALU_MFMA_COEXEC_CYCLES GRBM_GUI_ACTIVE
 pass C TCC_HIT_sum TCC_MISS_sum GRBM_COUNT
-python3 scripts/ctr_summary.py "$OUT" "$OUT/summary.json" k_gemm_f1_256_batch > "$OUT/summary.log" 2>&1
+python3 scripts/ctr_summary.py "$OUT" "$OUT/summary.json" k_gemm_f1h_batch > "$OUT/summary.log" 2>&1
 cat "$OUT/timing.log" "$OUT/summary.log"

@@ -208,3 +208,34 @@ def test_gemm_small_batch_validation(L):
         run(args(4096, 4, 4, 4, 4), args(4096, 4, 4, 4, 4, acc=0))
     with pytest.raises(ValueError, match="outputs overlap"):
         run(args(1 << 20, 8, 8, 4, 16), args((1 << 20) + 4 * 4, 8, 8, 4, 16))
+
+
+def test_gemm_workspace_bytes_pinned(L):
+    """The GEMM's split policy, read out through its two pure host functions, equals the table
+    recorded from the library before kernel selection moved to route_of
+    (tests/golden/gemm_workspace.json, tools/gemm_workspace_table.py): every route at a short
+    and two long K, both sides of each routing condition, and every batch class.  The workspace
+    is splits x (M N + rowsum entries) floats, so any change of route or split count shows."""
+    import json
+
+    table = json.load(open(os.path.join(ROOT, "tests", "golden", "gemm_workspace.json")))
+    lib = L.lib()
+
+    def args(case):
+        f = dict(table["defaults"], lda=case["M"], ldb=case["N"], ldc=case["N"])
+        f.update(case)
+        return L.AonGemmArgs(**f)
+
+    assert len(table["single"]) >= 150 and len(table["batch"]) >= 40
+    wrong = []
+    for row in table["single"]:
+        a = args(row["args"])
+        got = lib.aon_gemm_workspace_bytes(ctypes.byref(a))
+        if got != row["bytes"]:
+            wrong.append((row["name"], got, row["bytes"]))
+    for row in table["batch"]:
+        arr = (L.AonGemmArgs * len(row["args"]))(*[args(c) for c in row["args"]])
+        got = lib.aon_gemm_batch_workspace_bytes(arr, len(arr))
+        if got != row["bytes"]:
+            wrong.append((row["name"], got, row["bytes"]))
+    assert not wrong, f"(case, bytes, recorded): {wrong}"

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """One launch of the parity mode's fine-level 256 x 256 weight-gradient batch (aon_gemm_batch's
-f16_single class, k_gemm_f1_256_batch: 8 products of K = 790,528 tiled fp32 rows, distinct
+f16_single class, k_gemm_f1h_batch: 8 products of K = 790,528 tiled fp32 rows, distinct
 operands) for counter passes (scripts/prof_f1_counters.sh); --reps N times it with HIP events."""
 import argparse
 import os

@@ -18,7 +18,8 @@ c_i64, c_int, c_float, c_size, vp = ctypes.c_int64, ctypes.c_int, ctypes.c_float
 
 # render precisions (aon_mlp_fwd): exact fp32 MFMA, the fp16x3 split on 16x16x32 MFMAs
 PREC = {"fp32": 0, "f16x3": 1}
-PREC_F16X3_TRAIN = 1  # the training forwards' fp16x3 stream (aon_mlp_fwd_train)
+# "f16x3" is the render stream: bottleneck_layer folded into views_linear.0 by the pack
+PREC_F16X3_TRAIN = 4  # the training forward's fp16x3 stream, unfolded (aon_mlp_fwd_train)
 PREC_BF16 = 2  # the training step's bf16 mode (aon_mlp_fwd_train_bf16, aon_mlp_bwd_bf16)
 ACT_NONE, ACT_VANILLA, ACT_ARTIC = 0, 1, 2
 # opacity term of aon_loss_masked (AON_OPACITY_*)

@@ -259,7 +259,8 @@ _HOOK = _torch_optim.register_optimizer_step_pre_hook(_optimizer_step_pre_hook)
 
 
 def _pack(P, dev, tag="", bf16=False):
-    """The f16x3 (or bf16) weight stream of one level's parameters, re-packed on every call (the
+    """The training forward's f16x3 (unfolded: L.PREC_F16X3_TRAIN, not the render's folded
+    stream) or bf16 weight stream of one level's parameters, re-packed on every call (the
     optimizer updates the parameters in place behind torch's version counters).  ``tag``: one
     buffer per level (its range-status word must survive until the optimizer step)."""
     prec = L.PREC_BF16 if bf16 else L.PREC_F16X3_TRAIN

@@ -253,9 +253,11 @@ using namespace aon;
 using namespace aon::mlp;
 
 extern "C" size_t aon_mlp_packed_bytes(int precision) {
-  // every precision uses the same block grid: fp32 tiles, or hi+lo fp16 pairs of equal size
-  // (bf16: bf16 weights in the hi blocks)
-  if (precision == AON_PREC_FP32 || precision == AON_PREC_F16X3 || precision == AON_PREC_BF16)
+  // fp32 and the training streams use the same block grid: fp32 tiles, or hi+lo fp16 pairs of
+  // equal size (bf16: bf16 weights in the hi blocks); the fp16x3 render stream has no bottleneck
+  // layer (mlp_layout.hpp kLayersHFold)
+  if (precision == AON_PREC_F16X3) return NetVanillaFoldH::kPackedBytes;
+  if (precision == AON_PREC_FP32 || precision == AON_PREC_F16X3_TRAIN || precision == AON_PREC_BF16)
     return kPackedBytesF32;
   return 0;
 }
@@ -282,7 +284,7 @@ extern "C" int aon_mlp_pack(const aon_mlp_params* prm, int precision, void* pack
                             aon_stream_t stream) {
   AON_REQUIRE(prm && packed, "null pointer");
   AON_REQUIRE(precision == AON_PREC_FP32 || precision == AON_PREC_F16X3 ||
-                  precision == AON_PREC_BF16,
+                  precision == AON_PREC_F16X3_TRAIN || precision == AON_PREC_BF16,
               "unsupported precision");
   AON_REQUIRE(aligned16(packed), "packed buffer must be 16-byte aligned");
   if (check_mlp_params(prm, __func__)) return -1;
@@ -300,7 +302,8 @@ extern "C" int aon_mlp_pack(const aon_mlp_params* prm, int precision, void* pack
     a.layers[i] = precision == AON_PREC_FP32 ? kLayers[i] : kLayersH[i];
   }
   if (precision != AON_PREC_FP32)
-    return pack_f16x3(a, packed, (hipStream_t)stream, precision == AON_PREC_BF16);
+    return pack_f16x3(a, packed, (hipStream_t)stream, precision == AON_PREC_BF16,
+                      precision == AON_PREC_F16X3);
   // the fp32 kernels never set the range-status word: cleared once here
   const hipError_t e = hipMemsetAsync(static_cast<char*>(packed) + kPackedBytesF32 - kStatusBytes, 0,
                                       kStatusBytes, (hipStream_t)stream);
@@ -315,6 +318,9 @@ static int mlp_launch(int mode, const void* packed, int precision, const float* 
                       const float* a1, const float* a2, const float* a3, int64_t B, int S,
                       int act, float* raw, aon_stream_t stream) {
   AON_REQUIRE(packed && raw && a0 && a1, "null pointer");
+  AON_REQUIRE(precision != AON_PREC_F16X3_TRAIN,
+              "AON_PREC_F16X3_TRAIN is the training forward's stream (aon_mlp_fwd_train): render "
+              "with an AON_PREC_F16X3 pack");
   AON_REQUIRE(precision == AON_PREC_FP32 || precision == AON_PREC_F16X3,
               "unsupported precision (AON_PREC_BF16 is the training forward's: aon_mlp_fwd_train_bf16)");
   AON_REQUIRE(B >= 0 && S >= 1, "bad shape");

@@ -43,7 +43,7 @@ __device__ __forceinline__ int enc_slot(int c, int k, int lo) { return BF ? 3 * 
 template <bool BF>
 __device__ __forceinline__ int venc_slot(int c, int lo) { return BF ? 3 * c + 2 : 6 * c + 4 + lo; }
 
-template <int NCOL, bool STORE, typename T, typename FP>
+template <typename Net, int NCOL, bool STORE, typename T, typename FP>
 __device__ __forceinline__ void vanilla_layers(FP& fp, Frag<2, NCOL>& enc, Frag<1, NCOL>& venc,
                                                Frag<8, NCOL>& x, Frag<8, NCOL>& y, f4* stash,
                                                float* bias_s, int g, int wave,
@@ -64,11 +64,11 @@ __device__ __forceinline__ void vanilla_layers(FP& fp, Frag<2, NCOL>& enc, Frag<
   T* const thv = reinterpret_cast<T*>(ts.hv);
   const int64_t hs = act_rows(N) * 256;  // one pts_linears output in ts.h
   const int64_t ms = act_rows(N) * 4;    // one layer's ReLU' bits in ts.masks
-  layer_h<NetVanillaH, L0, true>(fp, none, enc, x, bias_l, g, SP::make(th, 256, rows, N, g, ts.masks));
-  layer_h<NetVanillaH, L1, true>(fp, x, none, y, bias_l, g, SP::make(th + 1 * hs, 256, rows, N, g, ts.masks + 1 * ms));
-  layer_h<NetVanillaH, L2, true>(fp, y, none, x, bias_l, g, SP::make(th + 2 * hs, 256, rows, N, g, ts.masks + 2 * ms));
-  layer_h<NetVanillaH, L3, true>(fp, x, none, y, bias_l, g, SP::make(th + 3 * hs, 256, rows, N, g, ts.masks + 3 * ms));
-  layer_h<NetVanillaH, L4, true>(fp, y, none, x, bias_l, g, SP::make(th + 4 * hs, 256, rows, N, g, ts.masks + 4 * ms));
+  layer_h<Net, L0, true>(fp, none, enc, x, bias_l, g, SP::make(th, 256, rows, N, g, ts.masks));
+  layer_h<Net, L1, true>(fp, x, none, y, bias_l, g, SP::make(th + 1 * hs, 256, rows, N, g, ts.masks + 1 * ms));
+  layer_h<Net, L2, true>(fp, y, none, x, bias_l, g, SP::make(th + 2 * hs, 256, rows, N, g, ts.masks + 2 * ms));
+  layer_h<Net, L3, true>(fp, x, none, y, bias_l, g, SP::make(th + 3 * hs, 256, rows, N, g, ts.masks + 3 * ms));
+  layer_h<Net, L4, true>(fp, y, none, x, bias_l, g, SP::make(th + 4 * hs, 256, rows, N, g, ts.masks + 4 * ms));
 #pragma unroll
   for (int c = 0; c < NCOL && !AON_STASH_REGS; ++c)
 #pragma unroll
@@ -77,21 +77,30 @@ __device__ __forceinline__ void vanilla_layers(FP& fp, Frag<2, NCOL>& enc, Frag<
       if (!BF) enc.lo[k][c] = __builtin_bit_cast(h8, stash[64 * enc_slot<BF>(c, k, 1)]);
     }
   // skip: cat[h, enc] (model.py:102-103)
-  layer_h<NetVanillaH, L5, true>(fp, x, enc, y, bias_l, g, SP::make(th + 5 * hs, 256, rows, N, g, ts.masks + 5 * ms));
-  layer_h<NetVanillaH, L6, true>(fp, y, none, x, bias_l, g, SP::make(th + 6 * hs, 256, rows, N, g, ts.masks + 6 * ms));
-  layer_h<NetVanillaH, L7, true>(fp, x, none, y, bias_l, g, SP::make(th + 7 * hs, 256, rows, N, g, ts.masks + 7 * ms));
+  layer_h<Net, L5, true>(fp, x, enc, y, bias_l, g, SP::make(th + 5 * hs, 256, rows, N, g, ts.masks + 5 * ms));
+  layer_h<Net, L6, true>(fp, y, none, x, bias_l, g, SP::make(th + 6 * hs, 256, rows, N, g, ts.masks + 6 * ms));
+  layer_h<Net, L7, true>(fp, x, none, y, bias_l, g, SP::make(th + 7 * hs, 256, rows, N, g, ts.masks + 7 * ms));
   f4 dens[NCOL], rgb[NCOL];
-  head_h<NetVanillaH, LDEN>(fp, y, dens, bias_l, g);             // model.py:105-107
-  // bottleneck, no activation (model.py:109)
-  layer_h<NetVanillaH, LBOT, false>(fp, y, none, x, bias_l, g, SP::make(tbot, 256, rows, N, g));
+  head_h<Net, LDEN>(fp, y, dens, bias_l, g);             // model.py:105-107
+  constexpr bool FOLD = std::is_same<Net, NetVanillaFoldH>::value;
+  static_assert(!FOLD || !STORE, "the training forwards keep the bottleneck activation");
+  // bottleneck, no activation (model.py:109) -- the render stream has none: it is folded into
+  // the view layer's weights (mlp_layout.hpp kLayersHFold), which then reads h7 (y) itself
+  if constexpr (!FOLD)
+    layer_h<Net, LBOT, false>(fp, y, none, x, bias_l, g, SP::make(tbot, 256, rows, N, g));
 #pragma unroll
   for (int c = 0; c < NCOL && !AON_STASH_REGS; ++c) {
     venc.hi[0][c] = __builtin_bit_cast(h8, stash[64 * venc_slot<BF>(c, 0)]);
     if (!BF) venc.lo[0][c] = __builtin_bit_cast(h8, stash[64 * venc_slot<BF>(c, 1)]);
   }
-  // cat[bottleneck, enc_dir] + ReLU (:110-116)
-  layer_h<NetVanillaH, LVIEW, true>(fp, x, venc, y, bias_l, g, SP::make(thv, 128, rows, N, g, ts.masks + 8 * ms));
-  head_h<NetVanillaH, LRGB>(fp, y, rgb, bias_l, g);              // model.py:118
+  // cat[bottleneck, enc_dir] + ReLU (:110-116), rgb head (:118)
+  if constexpr (FOLD) {
+    layer_h<Net, LF_VIEW, true>(fp, y, venc, x, bias_l, g);
+    head_h<Net, LF_RGB>(fp, x, rgb, bias_l, g);
+  } else {
+    layer_h<Net, LVIEW, true>(fp, x, venc, y, bias_l, g, SP::make(thv, 128, rows, N, g, ts.masks + 8 * ms));
+    head_h<Net, LRGB>(fp, y, rgb, bias_l, g);
+  }
 
   if (g == 0) {
 #pragma unroll
@@ -114,7 +123,9 @@ __device__ __forceinline__ void vanilla_layers(FP& fp, Frag<2, NCOL>& enc, Frag<
 // MODE 0: (rays_o, rays_d, viewdirs, t) inputs; MODE 1: encoded x (N, 63), condition (B, 27).
 // BF: bf16 numerics (one bf16 MFMA per k-step; the kept activations stored as bf16) -- the
 // bf16 training mode; the stream then carries bf16 weights in its hi blocks (k_pack_h bf16).
-template <int MODE, int NCOL, bool STORE = false, bool BF = false>
+// Net: the stream's layer table -- NetVanillaFoldH for the render (no bottleneck layer),
+// NetVanillaH for the training forwards (STORE).
+template <int MODE, int NCOL, bool STORE = false, bool BF = false, typename Net = NetVanillaH>
 __global__ __launch_bounds__((GeomH<NCOL, BF>::kThreads), (GeomH<NCOL, BF>::kWavesPerSimd)) void k_mlp_fwd_f16x3(
     const f4* __restrict__ wstream, const float* __restrict__ bias_g, const float* __restrict__ in0,
     const float* __restrict__ in1, const float* __restrict__ in2, const float* __restrict__ in3,
@@ -123,23 +134,23 @@ __global__ __launch_bounds__((GeomH<NCOL, BF>::kThreads), (GeomH<NCOL, BF>::kWav
   // ONE __shared__ object: weight ring | bias table | per-lane stash of the encodings
   constexpr int kPer = stash_per<BF>() * NCOL;  // f4 per lane: enc 2 k-steps + venc 1, hi (& lo)
   constexpr int kStash = AON_STASH_REGS ? 0 : G::kWaves * 64 * kPer;
-  static_assert((kLdsWeights + kBiasFloats / 4 + kStash) * 16 <= 160 * 1024, "LDS");
-  __shared__ f4 smem[kLdsWeights + kBiasFloats / 4 + kStash];
+  static_assert((kLdsWeights + Net::kBiasFloats / 4 + kStash) * 16 <= 160 * 1024, "LDS");
+  __shared__ f4 smem[kLdsWeights + Net::kBiasFloats / 4 + kStash];
   float* bias_s = reinterpret_cast<float*>(smem + kLdsWeights);
-  f4* stash = smem + kLdsWeights + kBiasFloats / 4 + (threadIdx.x >> 6) * 64 * kPer +
+  f4* stash = smem + kLdsWeights + Net::kBiasFloats / 4 + (threadIdx.x >> 6) * 64 * kPer +
               (threadIdx.x & 63);  // lane-private slots: written and read by the same lane
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, j = lane & 15;
   const int64_t N = B * S;
 
-  WeightPipeP<NetVanillaH, G::kThreads, BF> p;
+  WeightPipeP<Net, G::kThreads, BF> p;
   p.wbuf = smem;
   p.src = wstream;
   p.tid = tid;
   p.lane = lane;
   p.start();
-  for (int i = tid; i < kBiasFloats; i += G::kThreads) bias_s[i] = bias_g[i];
+  for (int i = tid; i < Net::kBiasFloats; i += G::kThreads) bias_s[i] = bias_g[i];
 
   // layer-0 (enc) and view-layer (enc_dir) fragments: k-step k, lane group g, element e
   // <-> feature 32k + 8g + e of the encoding
@@ -224,18 +235,18 @@ __global__ __launch_bounds__((GeomH<NCOL, BF>::kThreads), (GeomH<NCOL, BF>::kWav
   }
 
   Frag<8, NCOL> x, y;
-  using WP = WeightPipeP<NetVanillaH, G::kThreads, BF>;
+  using WP = WeightPipeP<Net, G::kThreads, BF>;
   using T = typename std::conditional<BF, __bf16, float>::type;
   // wave-uniform branch (readfirstlane): the running range masks stay in SGPRs across it
   // (not the training forward: with its row stores the second copy spills)
   if (AON_STAGGER && NCOL == 1 && !STORE && __builtin_amdgcn_readfirstlane(wave) >= G::kWaves / 2) {
     FragPipe<WP, AON_PREFETCH, 4, BF> fp(p);
-    vanilla_layers<NCOL, STORE, T>(fp, enc, venc, x, y, stash, bias_s, g, wave, rows, N, act, raw, ts);
+    vanilla_layers<Net, NCOL, STORE, T>(fp, enc, venc, x, y, stash, bias_s, g, wave, rows, N, act, raw, ts);
   } else {
     FragPipe<WP, AON_PREFETCH, 0, BF> fp(p);
-    vanilla_layers<NCOL, STORE, T>(fp, enc, venc, x, y, stash, bias_s, g, wave, rows, N, act, raw, ts);
+    vanilla_layers<Net, NCOL, STORE, T>(fp, enc, venc, x, y, stash, bias_s, g, wave, rows, N, act, raw, ts);
   }
-  range_report(bias_g + kBiasFloats, ovf_of(x) | ovf_of(y) | enc.ovf | venc.ovf);
+  range_report(bias_g + Net::kBiasFloats, ovf_of(x) | ovf_of(y) | enc.ovf | venc.ovf);
 }
 
 // ---- packing: torch [out][ldw] fp32 -> hi/lo fp16 blocks (+ biases at activation scale), for
@@ -293,8 +304,18 @@ __global__ void k_pack_h(PackArgsH a, float* __restrict__ out_f) {
             ld = a.ldw2[li];
           }
         }
-        if (o < d.out_real && col >= 0)
-          w = a.tr[li] ? src[(int64_t)col * ld + o] : src[(int64_t)o * ld + col];
+        if (o < d.out_real && col >= 0) {
+          if (a.fold_w && li == a.fold_layer && k < d.ka) {
+            // folded segment A (PackArgsH fold_w): fp64 in index order, one rounding to fp32
+            double acc = 0.0;
+            for (int j = 0; j < a.fold_k; ++j)
+              acc = fma(static_cast<double>(src[(int64_t)o * ld + j]),
+                        static_cast<double>(a.fold_w[(int64_t)j * d.len_a + col]), acc);
+            w = static_cast<float>(acc);
+          } else {
+            w = a.tr[li] ? src[(int64_t)col * ld + o] : src[(int64_t)o * ld + col];
+          }
+        }
       }
 #if AON_F16X3_V2
       if (bf && !a.f16w) {  // bf16 layer: bf16(w), unscaled, in the compact (hi-only) stream
@@ -327,7 +348,16 @@ __global__ void k_pack_h(PackArgsH a, float* __restrict__ out_f) {
 #else
       const float bs = kActScale;
 #endif
-      bias_out[i] = (o < a.layers[li].out_real && a.b[li]) ? a.b[li][o] * bs : 0.f;
+      float b = (o < a.layers[li].out_real && a.b[li]) ? a.b[li][o] : 0.f;
+      if (a.fold_w && li == a.fold_layer && o < a.layers[li].out_real) {
+        // folded bias: b[o] + sum_j w[o][j] fold_b[j], fp64 in index order, rounded once
+        double acc = 0.0;
+        for (int j = 0; j < a.fold_k; ++j)
+          acc = fma(static_cast<double>(a.w[li][(int64_t)o * a.ldw[li] + j]),
+                    static_cast<double>(a.fold_b[j]), acc);
+        b = static_cast<float>(static_cast<double>(b) + acc);
+      }
+      bias_out[i] = b * bs;
     }
   }
 }
@@ -348,9 +378,27 @@ int pack_h(PackArgsH a, void* packed, hipStream_t stream) {
   return launch_status("aon_mlp_pack");
 }
 
-int pack_f16x3(const PackArgs& a, void* packed, hipStream_t stream, bool bf16) {
+int pack_f16x3(const PackArgs& a, void* packed, hipStream_t stream, bool bf16, bool fold) {
   PackArgsH h{};
   h.bf16 = bf16 ? 1 : 0;
+  if (fold) {
+    // the render stream: kLayersH without the bottleneck, folded into the view layer
+    for (int i = 0; i < kNumLayersFold; ++i) {
+      const int src = i < LBOT ? i : i + 1;
+      h.w[i] = a.w[src];
+      h.b[i] = a.b[src];
+      h.layers[i] = kLayersHFold[i];
+      h.ldw[i] = kLayersHFold[i].len_a + kLayersHFold[i].len_b;
+    }
+    h.fold_w = a.w[LBOT];
+    h.fold_b = a.b[LBOT];
+    h.fold_layer = LF_VIEW;
+    h.fold_k = kLayersH[LBOT].out_real;
+    h.n_layers = kNumLayersFold;
+    h.stream_blocks = NetVanillaFoldH::kStreamBlocks;
+    h.bias_floats = NetVanillaFoldH::kBiasFloats;
+    return pack_h(h, packed, stream);
+  }
   for (int i = 0; i < kNumLayers; ++i) {
     h.w[i] = a.w[i];
     h.b[i] = a.b[i];
@@ -368,12 +416,16 @@ int launch_f16x3(int mode, int ncol, const void* packed, const float* a0, const 
                  hipStream_t stream, const TrainStore* ts) {
   const int64_t N = B * S;
   const f4* ws = static_cast<const f4*>(packed);
-  const float* bias = reinterpret_cast<const float*>(static_cast<const char*>(packed) + kStreamBytesF32);
+  // the training forwards read the unfolded stream, the render the folded one
+  const bool train = mode == 2 || mode == 3;
+  const float* bias = reinterpret_cast<const float*>(
+      static_cast<const char*>(packed) +
+      (train ? NetVanillaH::kStreamBytes : NetVanillaFoldH::kStreamBytes));
 #define AON_LAUNCH_H(M, C)                                                                       \
-  hipLaunchKernelGGL((k_mlp_fwd_f16x3<M, C>),                                                    \
+  hipLaunchKernelGGL((k_mlp_fwd_f16x3<M, C, false, false, NetVanillaFoldH>),                     \
                      static_cast<int>((N + GeomH<C>::kRowsPerBlock - 1) / GeomH<C>::kRowsPerBlock), \
                      GeomH<C>::kThreads, 0, stream, ws, bias, a0, a1, a2, a3, B, S, act, raw)
-  if (mode == 2 || mode == 3) {  // training forward: MODE 0 inputs + activation stores
+  if (train) {  // training forward: MODE 0 inputs + activation stores
     const int grid = static_cast<int>((N + GeomH<1>::kRowsPerBlock - 1) / GeomH<1>::kRowsPerBlock);
     if (mode == 3) {  // bf16 training mode: 16 kBfNcolFwd samples per wave
       using GB = GeomH<kBfNcolFwd, true>;

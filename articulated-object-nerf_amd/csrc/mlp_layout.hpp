@@ -63,6 +63,32 @@ constexpr LayerDesc kLayersH[kNumLayers] = {
     {4, 0, 1, 128, 0, 3, 2336, 2448},
 };
 
+// The fp16x3 RENDER stream (inference: aon_mlp_fwd / aon_mlp_fwd_encoded): bottleneck_layer has
+// no activation (model.py:109) and feeds only views_linear.0, so the two linear maps are one --
+//   z_view = (Wv[:, :256] Wb) h7 + Wv[:, 256:] enc_dir + (bv + Wv[:, :256] bb)
+// -- and the stream holds no bottleneck layer: the view layer's segment A is h7 with the folded
+// 128 x 256 weight, formed by the pack (k_pack_h fold_w).  65,536 of the 593,408 MAC per sample
+// (11%) and 256 of the 2,344 blocks go.  The training forwards keep the unfolded kLayersH stream
+// (they store the bottleneck activation for the backward).
+enum { LF_VIEW = LDEN + 1, LF_RGB, kNumLayersFold };
+
+constexpr LayerDesc kLayersHFold[kNumLayersFold] = {
+    {0, 2, 16, 0, 63, 256, 0, 0},             // pts_linears.0: enc only (segment B)
+    {8, 0, 16, 256, 0, 256, 64, 256},
+    {8, 0, 16, 256, 0, 256, 320, 512},
+    {8, 0, 16, 256, 0, 256, 576, 768},
+    {8, 0, 16, 256, 0, 256, 832, 1024},
+    {8, 2, 16, 256, 63, 256, 1088, 1280},
+    {8, 0, 16, 256, 0, 256, 1408, 1536},
+    {8, 0, 16, 256, 0, 256, 1664, 1792},
+    {8, 0, 1, 256, 0, 1, 1920, 2048},         // density_layer
+    {8, 1, 8, 256, 27, 128, 1936, 2064},      // views_linear.0 . [bottleneck_layer | I]: 128 x (256 + 27)
+    {4, 0, 1, 128, 0, 3, 2080, 2192},         // rgb_layer
+};
+constexpr int kBlocksFold = 2088;                                  // kBlocks - 256
+constexpr int kStreamBlocksFold = (kBlocksFold + 63) / 64 * 64;   // 2112
+constexpr int kBiasFloatsFold = 2208;                              // kBiasFloats - 256
+
 // V1 numerics (AON_F16X3_V2 = 0, kept for A/B only): activations and biases carried at 2^-8,
 // lo halves at 2^11, two accumulators
 constexpr float kActScale = 1.0f / 256.0f;
@@ -227,10 +253,28 @@ struct NetH {
 };
 
 using NetVanillaH = NetH<kLayersH, kNumLayers, kBlocks, kStreamBlocks, kBiasFloats>;
+using NetVanillaFoldH =
+    NetH<kLayersHFold, kNumLayersFold, kBlocksFold, kStreamBlocksFold, kBiasFloatsFold>;
 using NetArtH = NetH<kLayersArt, kNumLayersArt, 2752, 2752, 3376>;
 using NetBwdH = NetH<kLayersBwd, kNumLayersBwd, 2224, 2240, 2432, true>;
 using NetArtBwdH = NetH<kLayersArtBwd, kNumLayersArtBwd, 2752, 2752, 3456, true>;
 static_assert(NetVanillaH::ok(), "inconsistent vanilla fp16x3 layout");
+static_assert(NetVanillaFoldH::ok(), "inconsistent folded vanilla fp16x3 layout");
+// the folded table is kLayersH without LBOT: same trunk and heads, the view layer on h7
+constexpr bool layout_fold_ok() {
+  for (int i = 0; i < kNumLayersFold; ++i) {
+    const LayerDesc& f = kLayersHFold[i];
+    const LayerDesc& h = kLayersH[i < LBOT ? i : i + 1];
+    if (f.ka != h.ka || f.kb != h.kb || f.u != h.u || f.len_a != h.len_a || f.len_b != h.len_b ||
+        f.out_real != h.out_real)
+      return false;
+    if (i < LBOT && (f.blk0 != h.blk0 || f.bias0 != h.bias0)) return false;
+  }
+  const LayerDesc& b = kLayersH[LBOT];
+  return kLayersHFold[LF_VIEW].len_a == b.out_real && kBlocksFold == kBlocks - b.ka * b.u * 2 &&
+         kBiasFloatsFold == kBiasFloats - b.u * 16;
+}
+static_assert(layout_fold_ok(), "folded layout must be kLayersH without the bottleneck");
 static_assert(NetArtH::ok(), "inconsistent articulated fp16x3 layout");
 static_assert(NetBwdH::ok(), "inconsistent backward-chain fp16x3 layout");
 static_assert(NetArtBwdH::ok(), "inconsistent articulated backward-chain fp16x3 layout");
@@ -264,6 +308,14 @@ struct PackArgsH {
   // compact blocks (modes 1, 2) hold fp16(w 2^6) instead of bf16(w), range-guarded like the
   // fp16x3 hi blocks, and their layers' biases are at activation scale (FragPipe W1)
   int f16w;
+  // fold_w set: layer fold_layer's segment A is the product of its own first fold_k columns
+  // with the linear layer in front of it (fold_w [fold_k][len_a], fold_b [fold_k]; no
+  // activation between them): stream element (o, col) = fp32(sum_j w[o][j] fold_w[j][col]),
+  // bias fp32(b[o] + sum_j w[o][j] fold_b[j]), both summed in fp64 in index order -- then
+  // scaled, split and range-tested like any other weight (the render stream's view layer)
+  const float* fold_w;
+  const float* fold_b;
+  int fold_layer, fold_k;
 };
 
 // Where the weight stream holds fp16x3 block b (even b: the hi block of a (hi, lo) pair, b + 1
@@ -345,7 +397,9 @@ struct TrainStoreArt {
 };
 
 // fp16x3 path (mlp_f16x3.hip)
-int pack_f16x3(const PackArgs& a, void* packed, hipStream_t stream, bool bf16 = false);
+// fold: the render stream (NetVanillaFoldH), else the training forwards' (NetVanillaH)
+int pack_f16x3(const PackArgs& a, void* packed, hipStream_t stream, bool bf16 = false,
+               bool fold = false);
 int pack_h(PackArgsH a, void* packed, hipStream_t stream);
 // *out = bits of max |x| over n floats (memset + k_absmax, mlp_bwd.hip): the backward chains'
 // per-call gradient scale

@@ -346,7 +346,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_mlp_ws_f16x3(
     const f4* __restrict__ wstream, const float* __restrict__ bias_g, const float* __restrict__ in0,
     const float* __restrict__ in1, const float* __restrict__ in2, const float* __restrict__ in3,
     int64_t B, int S, int act, float* __restrict__ raw) {
-  using Net = NetVanillaH;
+  using Net = NetVanillaFoldH;  // the render stream: no bottleneck layer (mlp_layout.hpp)
   using G = Geo<WAVES>;
   __shared__ f4 smem[G::kLdsF4];
   const int64_t N = B * S;
@@ -395,11 +395,11 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_mlp_ws_f16x3(
   });
   hidden_layer<Net, G, L6, true>(ap, pl, bias_g, w, g, m16);
   hidden_layer<Net, G, L7, true>(ap, pl, bias_g, w, g, m16);
-  // density head on h7 (this wave's tile), then the bottleneck (no activation) on h7
+  // density head on h7 (this wave's tile), then the view layer on cat[h7, enc_dir] + ReLU (the
+  // bottleneck is folded into its weights)
   const f4 dens = head<Net, G, LDEN>(ap, pl, bias_g, w, g);
-  hidden_layer<Net, G, LBOT, false>(ap, pl, bias_g, w, g, m16);
-  hidden_layer<Net, G, LVIEW, true>(ap, pl, bias_g, w, g, m16);  // cat[bottleneck, enc_dir] + ReLU
-  const f4 rgb = head<Net, G, LRGB>(ap, pl, bias_g, w, g);
+  hidden_layer<Net, G, LF_VIEW, true>(ap, pl, bias_g, w, g, m16);
+  const f4 rgb = head<Net, G, LF_RGB>(ap, pl, bias_g, w, g);
   if (g == 0 && c.row < N) {
     const f4 o = {act_rgb(rgb[0], act), act_rgb(rgb[1], act), act_rgb(rgb[2], act), act_sigma(dens[0], act)};
     *reinterpret_cast<f4*>(raw + 4 * c.row) = o;
@@ -772,7 +772,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_mlp_ws_pipe_f16x3(
     const f4* __restrict__ wstream, const float* __restrict__ bias_g, const float* __restrict__ in0,
     const float* __restrict__ in1, const float* __restrict__ in2, const float* __restrict__ in3,
     int64_t B, int S, int act, float* __restrict__ raw) {
-  using Net = NetVanillaH;
+  using Net = NetVanillaFoldH;  // the render stream: no bottleneck layer (mlp_layout.hpp)
   using G = Geo<WAVES>;
   __shared__ f4 smem[G::kLdsF4];
   const int64_t N = B * S;
@@ -823,27 +823,27 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_mlp_ws_pipe_f16x3(
   }
   AON_WS_HALVES(L6, true, j5, j6)
   AON_WS_HALVES(L7, true, j6, j7)
-  // the bottleneck's halves; the density head reads h7 of the wave's tile while it is complete
-  // and not yet overwritten: tiles of half 0 during the bottleneck's half 0 (j7 writes half 1),
-  // tiles of half 1 during its half 1 (its half-0 job writes half 0)
+  // the view layer's halves (cat[h7, enc_dir] + ReLU, the bottleneck folded into its weights);
+  // the density head reads h7 of the wave's tile while it is complete and not yet overwritten:
+  // tiles of half 0 during the view layer's half 0 (j7 writes half 1), tiles of half 1 during
+  // its half 1 (its half-0 job writes half 0)
   f4 dens = {0.f, 0.f, 0.f, 0.f};
   if (first_half) dens = head_direct<Net, G, LDEN>(pl, wstream, bias_g, w, g, c.lane);
-  f4 jb_a0[LG<Net, G, LBOT>::TU][LG<Net, G, LBOT>::NTh];
-  half_mfma<Net, G, LBOT, 0>(ap, pl, w, jb_a0, j7, m16);
+  f4 jv_a0[LG<Net, G, LF_VIEW>::TU][LG<Net, G, LF_VIEW>::NTh];
+  half_mfma<Net, G, LF_VIEW, 0>(ap, pl, w, jv_a0, j7, m16);
   lds_barrier();
-  const auto jb_j0 = make_job<Net, G, LBOT, false, 0>(jb_a0, bias_g, w, g);
+  const auto jv_j0 = make_job<Net, G, LF_VIEW, true, 0>(jv_a0, bias_g, w, g);
   if (!first_half) dens = head_direct<Net, G, LDEN>(pl, wstream, bias_g, w, g, c.lane);
-  f4 jb_a1[LG<Net, G, LBOT>::TU][LG<Net, G, LBOT>::NTh];
-  half_mfma<Net, G, LBOT, 1>(ap, pl, w, jb_a1, jb_j0, m16);
+  f4 jv_a1[LG<Net, G, LF_VIEW>::TU][LG<Net, G, LF_VIEW>::NTh];
+  half_mfma<Net, G, LF_VIEW, 1>(ap, pl, w, jv_a1, jv_j0, m16);
   lds_barrier();
-  const auto jb = make_job<Net, G, LBOT, false, 1>(jb_a1, bias_g, w, g);
-  AON_WS_HALVES(LVIEW, true, jb, jv)  // cat[bottleneck, enc_dir] + ReLU
+  const auto jv = make_job<Net, G, LF_VIEW, true, 1>(jv_a1, bias_g, w, g);
   // the view layer's half-1 epilogue; the rgb head of half-0 tiles meanwhile (hv complete there)
   f4 rgb;
-  if (first_half) rgb = head_direct<Net, G, LRGB>(pl, wstream, bias_g, w, g, c.lane);
+  if (first_half) rgb = head_direct<Net, G, LF_RGB>(pl, wstream, bias_g, w, g, c.lane);
   jv.all(pl, m16);
   lds_barrier();
-  if (!first_half) rgb = head_direct<Net, G, LRGB>(pl, wstream, bias_g, w, g, c.lane);
+  if (!first_half) rgb = head_direct<Net, G, LF_RGB>(pl, wstream, bias_g, w, g, c.lane);
   if (g == 0 && c.row < N) {
     const f4 o = {act_rgb(rgb[0], act), act_rgb(rgb[1], act), act_rgb(rgb[2], act), act_sigma(dens[0], act)};
     *reinterpret_cast<f4*>(raw + 4 * c.row) = o;
@@ -874,7 +874,8 @@ int launch_ws_f16x3(const void* packed, const float* a0, const float* a1, const 
                     const float* a3, int64_t B, int S, int act, float* raw, hipStream_t stream) {
   const int64_t N = B * S;
   const f4* wsp = static_cast<const f4*>(packed);
-  const float* bias = reinterpret_cast<const float*>(static_cast<const char*>(packed) + kStreamBytesF32);
+  const float* bias = reinterpret_cast<const float*>(static_cast<const char*>(packed) +
+                                                    NetVanillaFoldH::kStreamBytes);
   if (ws_pipe() && ws_waves() == 8)
     hipLaunchKernelGGL(ws::k_mlp_ws_pipe_f16x3<8>, static_cast<int>((N + 127) / 128), 512, 0,
                        stream, wsp, bias, a0, a1, a2, a3, B, S, act, raw);

@@ -29,12 +29,23 @@ typedef void* aon_stream_t; /* hipStream_t */
                             * (value 3) withdrawn: measured slower.
                             * Added since, without a version change (purely additive):
                             * aon_ssim_workspace_bytes, aon_image_ssim, aon_ssim_tile,
-                            * aon_loss_masked, aon_loss_masked_bwd */
+                            * aon_loss_masked, aon_loss_masked_bwd; AON_PREC_F16X3_TRAIN (the
+                            * AON_PREC_F16X3 stream now has bottleneck_layer folded in) */
 
 /* Precision of the MLP GEMMs (see DESIGN.md "MLP precision modes"). */
 #define AON_PREC_FP32 0  /* exact fp32 MFMA (v_mfma_f32_16x16x4_f32) */
 #define AON_PREC_F16X3 1 /* fp16 hi/lo split, 3 products (hi*hi + hi*lo + lo*hi) per weight on
-                            v_mfma_f32_16x16x32_f16, fp32 accumulate: ~22-bit operands */
+                            v_mfma_f32_16x16x32_f16, fp32 accumulate: ~22-bit operands.  The
+                            RENDER stream (aon_mlp_pack / aon_mlp_packed_bytes -> aon_mlp_fwd,
+                            aon_mlp_fwd_encoded): bottleneck_layer has no activation and feeds
+                            only views_linear.0, so the pack folds it into that layer
+                            (W' = Wv[:, :256] Wb, b' = bv + Wv[:, :256] bb, summed in fp64 and
+                            rounded once to fp32) and the stream has no bottleneck layer */
+#define AON_PREC_F16X3_TRAIN 4 /* the same numerics, the UNFOLDED stream (bottleneck_layer as its
+                                * own layer): what aon_mlp_fwd_train consumes -- it keeps the
+                                * bottleneck activation for the backward.  aon_mlp_pack and
+                                * aon_mlp_packed_bytes take it; aon_mlp_fwd[_encoded] refuse it.
+                                * (3 stays withdrawn.) */
 #define AON_PREC_BF16 2  /* bf16 operands, 1 product per weight (v_mfma_f32_16x16x32_bf16), fp32
                          * accumulate: the training step's bf16 mode (BASELINE config C5) --
                          * aon_mlp_fwd_train_bf16 / aon_mlp_bwd_bf16 / aon_gemm with bf16 operands */
@@ -159,8 +170,13 @@ typedef struct aon_mlp_params {
   int64_t w_rows[12], w_cols[12], b_len[12];
 } aon_mlp_params;
 
+/* Which stream each entry point takes: aon_mlp_fwd / aon_mlp_fwd_encoded AON_PREC_FP32 or
+ * AON_PREC_F16X3 (passed to them again as `precision`); aon_mlp_fwd_train AON_PREC_F16X3_TRAIN;
+ * aon_mlp_fwd_train_bf16 AON_PREC_BF16.  The streams differ in size: ask per precision. */
 size_t aon_mlp_packed_bytes(int precision);
-/* Re-lay the parameters into the MFMA-tiled weight stream consumed by aon_mlp_fwd. */
+/* Re-lay the parameters into the MFMA-tiled weight stream of `precision`.  The status block
+ * reports 2 for a weight the stream cannot hold -- for AON_PREC_F16X3's view layer that is the
+ * folded weight W', not its factors. */
 int aon_mlp_pack(const aon_mlp_params* params, int precision, void* packed,
                  aon_stream_t stream);
 
@@ -206,7 +222,7 @@ int aon_mlp_fwd_encoded(const void* packed, int precision, const float* x,
  * h (8, NR, 256) are NR rows apart.  aon_gemm reads them in place (a_tiled / b_tiled).
  *
  * The training forward of one level (model.py:175-184 under autograd) on the fused fp16x3
- * kernel: as aon_mlp_fwd with AON_ACT_NONE (packed = AON_PREC_F16X3 stream), plus every
+ * kernel: as aon_mlp_fwd with AON_ACT_NONE (packed = AON_PREC_F16X3_TRAIN stream), plus every
  * hidden activation kept for the backward (tiled, NR = B*S rounded up to 16 rows) -- h (8, NR,
  * 256): post-ReLU pts_linears.0..7, bot (NR, 256): bottleneck_layer, hv (NR, 128): post-ReLU
  * views_linear.0 -- and raw_sigma + noise[row] when noise (B*S) is not NULL.  masks (9, NR, 4) pairs of uint32:

@@ -9,6 +9,9 @@ loads unchanged.  The forward pass runs on the fused HIP kernels:
              sample_pdf: the coarse weights stay on chip; NeRF.fused_march / march_ok)
     level 1: aon_mlp_fwd on the merged t -> aon_composite_fwd
     (fused_march False, or N_importance > 256: aon_composite_fwd + aon_sample_pdf, bit-identical)
+    fine_only (what aonerf.render asks for), f16x3: level 0's MLP is the density-only pass
+    aon_mlp_fwd_sigma, level 1's reads per-ray view encodings (aon_pos_enc once per forward,
+    aon_mlp_fwd_cond) -- the fine level's outputs are the same bits
 
 Per-model configuration only (no mutable globals): the render precision
 (``precision``), the training numerics (``train_precision`` / ``train_numerics``,
@@ -104,15 +107,35 @@ class NeRFMLP(nn.Module):
             self._packed, self._packed_key = buf, key
         return self._packed
 
-    def forward_rays(self, rays_o, rays_d, viewdirs, t_vals, act=L.ACT_NONE):
+    def forward_rays(self, rays_o, rays_d, viewdirs, t_vals, act=L.ACT_NONE, cond=None):
         """Fused cast_rays + pos_enc + forward: (B*S, 4) = [raw_rgb, raw_sigma]; with
-        ``act=L.ACT_VANILLA`` the rgb/sigma activations of model.py:186-187 are applied too."""
-        L.require_gpu(rays_o, rays_d, viewdirs, t_vals)
+        ``act=L.ACT_VANILLA`` the rgb/sigma activations of model.py:186-187 are applied too.
+        ``cond`` (B, 27) = pos_enc(viewdirs, 0, deg_view), f16x3 only: the view encodings are read
+        from it (aon_mlp_fwd_cond) instead of recomputed per sample -- the same bits."""
+        L.require_gpu(rays_o, rays_d, viewdirs, t_vals, cond)
         B, S = t_vals.shape
         raw = torch.empty((B * S, 4), device=t_vals.device)
+        if cond is not None:
+            if tuple(cond.shape) != (B, 27):
+                raise ValueError("forward_rays expects cond (B, 27)")
+            L.call("aon_mlp_fwd_cond", L.ptr(self.packed_weights()), L.PREC[self.precision],
+                   L.ptr(L.contig(rays_o)), L.ptr(L.contig(rays_d)), L.ptr(L.contig(cond)),
+                   L.ptr(L.contig(t_vals)), B, S, act, L.ptr(raw), L.stream(t_vals.device))
+            return raw
         L.call("aon_mlp_fwd", L.ptr(self.packed_weights()), L.PREC[self.precision],
                L.ptr(L.contig(rays_o)), L.ptr(L.contig(rays_d)), L.ptr(L.contig(viewdirs)),
                L.ptr(L.contig(t_vals)), B, S, act, L.ptr(raw), L.stream(t_vals.device))
+        return raw
+
+    def forward_sigma(self, rays_o, rays_d, t_vals, act=L.ACT_NONE):
+        """The density-only pass (aon_mlp_fwd_sigma, f16x3 only): (B*S, 4) = [0, 0, 0, sigma],
+        column 3 as forward_rays returns it; no view layer, rgb head or view encoding runs."""
+        L.require_gpu(rays_o, rays_d, t_vals)
+        B, S = t_vals.shape
+        raw = torch.empty((B * S, 4), device=t_vals.device)
+        L.call("aon_mlp_fwd_sigma", L.ptr(self.packed_weights()), L.PREC[self.precision],
+               L.ptr(L.contig(rays_o)), L.ptr(L.contig(rays_d)), L.ptr(L.contig(t_vals)), B, S, act,
+               L.ptr(raw), L.stream(t_vals.device))
         return raw
 
     def forward(self, x, condition):
@@ -231,7 +254,7 @@ class NeRF(nn.Module):
         return self
 
     def forward(self, rays, randomized, white_bkgd, near, far, *, u_coarse=None, u_fine=None,
-                return_weights=False, return_intermediates=False, timers=None):
+                return_weights=False, return_intermediates=False, timers=None, fine_only=False):
         """reference model.py:147-199 -> [(comp_rgb, acc, depth)_coarse, (...)_fine].
 
         ``u_coarse`` (B, Sc+1) / ``u_fine`` (B, Nf) inject the uniforms of randomized mode;
@@ -240,7 +263,14 @@ class NeRF(nn.Module):
         (rgb_sigma (B*S, 4), inference path only: the activated MLP outputs the compositor
         consumed);
         ``timers`` (dict) records hip events around each level's MLP / composite launches (the
-        training path: around its fused training kernels).
+        training path: around its fused training kernels);
+        ``fine_only`` (inference path, without ``return_weights`` / ``return_intermediates``): the
+        caller keeps only the fine level, so the coarse level's colour is not computed and the
+        first element is None.  The fine level is the same, bit for bit: the coarse level reaches
+        it through its weights alone, which read sigma and t.  On f16x3 the coarse MLP then runs
+        the density-only kernel (aon_mlp_fwd_sigma) and the fine MLP reads the per-ray view
+        encodings, formed once per forward (aon_pos_enc), instead of recomputing them per sample
+        (aon_mlp_fwd_cond); fp32 has no such kernels and runs aon_mlp_fwd.
 
         With autograd enabled and trainable parameters, each level runs the training path
         (train.RenderLevel: the fused training forward aon_mlp_fwd_train, which also stores the
@@ -253,6 +283,9 @@ class NeRF(nn.Module):
         training = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
         B = o.shape[0]
         dev = o.device
+        fine_only = bool(fine_only) and not (training or return_weights or return_intermediates)
+        two_pass = fine_only and self.coarse_mlp.precision == self.fine_mlp.precision == "f16x3"
+        cond = helper.pos_enc(v, 0, self.deg_view) if two_pass else None
         # the fp16x3 overflow fallback below re-renders with the same random draws (density
         # noise, stratified t, fine u) and leaves the generator where one forward leaves it
         rng = torch.cuda.get_rng_state(dev) if randomized and not training else None
@@ -298,6 +331,7 @@ class NeRF(nn.Module):
             with torch.no_grad():
                 out, weights, t_next = self._render_level_fused(
                     mlp, o, d, v, t_vals, randomized, white_bkgd, level, timers, keep_w,
+                    sigma_only=two_pass and level == 0, cond=cond if level == 1 else None,
                     # drawn inside, after the level's density noise (the reference's RNG order)
                     march_u=(lambda: fine_uniforms(B, self.num_fine_samples, randomized, dev,
                                                    u_fine)) if march else None)
@@ -305,7 +339,7 @@ class NeRF(nn.Module):
                 out = out[:3] + out[4:]
             if not return_intermediates:
                 out = out[:4] if return_weights else out[:3]
-            ret.append(out)
+            ret.append(None if fine_only and level == 0 else out)
         if (not training and self.range_check and self.coarse_mlp.precision.startswith("f16x3")
                 and not torch.cuda.is_current_stream_capturing()
                 and L.range_overflow([self.coarse_mlp._packed, self.fine_mlp._packed])):
@@ -320,7 +354,8 @@ class NeRF(nn.Module):
             try:
                 return self.forward(rays, randomized, white_bkgd, near, far, u_coarse=u_coarse,
                                     u_fine=u_fine, return_weights=return_weights,
-                                    return_intermediates=return_intermediates, timers=timers)
+                                    return_intermediates=return_intermediates, timers=timers,
+                                    fine_only=fine_only)
             finally:
                 self.set_precision(prec)
         return ret
@@ -331,17 +366,23 @@ class NeRF(nn.Module):
                             u_coarse, u_fine)
 
     def _render_level_fused(self, mlp, o, d, v, t_vals, randomized, white_bkgd, level, timers,
-                            keep_weights=True, march_u=None):
+                            keep_weights=True, march_u=None, sigma_only=False, cond=None):
         """One inference level: fused MLP, then compositing -- with ``march_u`` (a callable
         returning the fine level's (u, u_stride)) also the next level's resampling in the same
-        kernel (returned t_next, else None)."""
+        kernel (returned t_next, else None).  ``sigma_only``: the density-only MLP pass (the
+        level's colour comes out as the compositor's of a zero rgb: only its weights and t_next
+        mean anything); ``cond``: the per-ray view encodings (forward_rays)."""
         B, S = t_vals.shape
         dev = o.device
         # the activations (model.py:186-187) run in the MLP epilogue, unless density noise
         # must be added to the raw sigma first (model.py:183-184)
         noisy = self.noise_std > 0 and randomized
         ev = _events(timers)
-        raw = mlp.forward_rays(o, d, v, t_vals, act=L.ACT_NONE if noisy else L.ACT_VANILLA)
+        act = L.ACT_NONE if noisy else L.ACT_VANILLA
+        if sigma_only:
+            raw = mlp.forward_sigma(o, d, t_vals, act=act)
+        else:
+            raw = mlp.forward_rays(o, d, v, t_vals, act=act, cond=cond)
         _record(timers, ev, f"mlp{level}", B * S)
         if noisy:
             raw[:, 3] += torch.rand_like(raw[:, 3]) * self.noise_std

@@ -30,7 +30,7 @@ def render_rays(model, batch, chunk, white_bkgd, near, far):
     ret = defaultdict(list)
     for i, j in _chunks(B, chunk):
         sub = {k: batch[k][i:j] for k in ("rays_o", "rays_d", "viewdirs")}
-        fine = model(sub, False, white_bkgd, near, far)[1]
+        fine = model(sub, False, white_bkgd, near, far, fine_only=True)[1]
         ret["comp_rgb"].append(fine[0])
         ret["acc"].append(fine[1])
         ret["depth"].append(fine[2])
@@ -62,7 +62,7 @@ def render_frame(model, c2w, H, W, focal, near=2.0, far=6.0, white_bkgd=True, p0
     out = torch.empty((n, 5), device=rays["rays_o"].device)
     for i, j in _chunks(n, chunk):
         sub = {k: v[i:j] for k, v in rays.items()}
-        fine = model(sub, False, white_bkgd, near, far, timers=timers)[1]
+        fine = model(sub, False, white_bkgd, near, far, timers=timers, fine_only=True)[1]
         out[i:j, 0:3] = fine[0]
         out[i:j, 3] = fine[2]
         out[i:j, 4] = fine[1]

@@ -361,6 +361,43 @@ extern "C" int aon_mlp_fwd_encoded(const void* packed, int precision, const floa
   return mlp_launch(1, packed, precision, x, condition, nullptr, nullptr, B, S, act, raw, stream);
 }
 
+// the checks aon_mlp_fwd_sigma / aon_mlp_fwd_cond share, before any launch; 1: nothing to do
+static int two_pass_check(const void* packed, int precision, const float* rays_o,
+                          const float* rays_d, const float* t, int64_t B, int S, int act,
+                          const float* raw) {
+  AON_REQUIRE(packed && raw && rays_o && rays_d && t, "null pointer");
+  AON_REQUIRE(precision != AON_PREC_F16X3_TRAIN,
+              "AON_PREC_F16X3_TRAIN is the training forward's stream (aon_mlp_fwd_train): render "
+              "with an AON_PREC_F16X3 pack");
+  AON_REQUIRE(precision != AON_PREC_FP32,
+              "AON_PREC_FP32 has no two-pass kernels: render a fp32 pack with aon_mlp_fwd");
+  AON_REQUIRE(precision == AON_PREC_F16X3,
+              "unsupported precision (AON_PREC_BF16 is the training forward's: aon_mlp_fwd_train_bf16)");
+  AON_REQUIRE(B >= 0 && S >= 1, "bad shape");
+  AON_REQUIRE(act >= AON_ACT_NONE && act <= AON_ACT_ARTIC, "bad activation");
+  AON_REQUIRE(aligned16(packed) && aligned16(raw), "packed / raw must be 16-byte aligned");
+  if (B * S == 0) return 1;
+  AON_REQUIRE((B * S + 127) / 128 < (1ll << 31), "too many rows");
+  return 0;
+}
+
+extern "C" int aon_mlp_fwd_sigma(const void* packed, int precision, const float* rays_o,
+                                 const float* rays_d, const float* t, int64_t B, int S, int act,
+                                 float* raw, aon_stream_t stream) {
+  const int c = two_pass_check(packed, precision, rays_o, rays_d, t, B, S, act, raw);
+  if (c) return c < 0 ? c : 0;
+  return launch_f16x3_sigma(packed, rays_o, rays_d, t, B, S, act, raw, (hipStream_t)stream);
+}
+
+extern "C" int aon_mlp_fwd_cond(const void* packed, int precision, const float* rays_o,
+                                const float* rays_d, const float* cond, const float* t, int64_t B,
+                                int S, int act, float* raw, aon_stream_t stream) {
+  AON_REQUIRE(cond, "null pointer");
+  const int c = two_pass_check(packed, precision, rays_o, rays_d, t, B, S, act, raw);
+  if (c) return c < 0 ? c : 0;
+  return launch_f16x3_cond(packed, rays_o, rays_d, cond, t, B, S, act, raw, (hipStream_t)stream);
+}
+
 extern "C" int aon_mlp_fwd_train(const void* packed, const float* rays_o, const float* rays_d,
                                  const float* viewdirs, const float* t, int64_t B, int S,
                                  const float* noise, float* h, float* bot, float* hv, float* raw,

@@ -35,13 +35,25 @@ namespace mlp {
 // The layer sequence of k_mlp_fwd_f16x3 (model.py:95-120), instantiated per FragPipe type: the
 // two halves of the workgroup differ in the k-step of their epilogues (FragPipe EOFF).
 // per-lane LDS stash of the encodings: enc k-steps 0, 1 and venc, hi and lo (fp16x3) or hi only
-// (bf16: no lo part); slot (c, i) at stash[64 (kStashPer c + i)]
-template <bool BF>
-__host__ __device__ constexpr int stash_per() { return BF ? 3 : 6; }
-template <bool BF>
-__device__ __forceinline__ int enc_slot(int c, int k, int lo) { return BF ? 3 * c + k : 6 * c + 2 * k + lo; }
+// (bf16: no lo part); slot (c, i) at stash[64 (kStashPer c + i)].  SIG (the density-only pass):
+// no venc slots
+template <bool BF, bool SIG = false>
+__host__ __device__ constexpr int stash_per() { return BF ? 3 : (SIG ? 4 : 6); }
+template <bool BF, bool SIG = false>
+__device__ __forceinline__ int enc_slot(int c, int k, int lo) {
+  return BF ? 3 * c + k : stash_per<BF, SIG>() * c + 2 * k + lo;
+}
 template <bool BF>
 __device__ __forceinline__ int venc_slot(int c, int lo) { return BF ? 3 * c + 2 : 6 * c + 4 + lo; }
+
+// the density-only pass (mlp_layout.hpp NetVanillaSigmaH): the trunk and the density head
+template <typename Net>
+constexpr bool kSigmaOnly = std::is_same<Net, NetVanillaSigmaH>::value;
+// the ring chunks of the prefix: whole chunks, and the last one holds a block the pass reads, so
+// every copy the ring issues is waited for (DmaPipe::begin) before the kernel ends
+static_assert(kStreamBlocksSigma % kChunkH == 0 &&
+                  (kBlocksSigma - 1) / kChunkH == kStreamBlocksSigma / kChunkH - 1,
+              "density-only stream: whole ring chunks, none unused");
 
 template <typename Net, int NCOL, bool STORE, typename T, typename FP>
 __device__ __forceinline__ void vanilla_layers(FP& fp, Frag<2, NCOL>& enc, Frag<1, NCOL>& venc,
@@ -50,6 +62,8 @@ __device__ __forceinline__ void vanilla_layers(FP& fp, Frag<2, NCOL>& enc, Frag<
                                                const int64_t (&rows)[NCOL], int64_t N, int act,
                                                float* __restrict__ raw, const TrainStore& ts) {
   constexpr bool BF = std::is_same<T, __bf16>::value;
+  constexpr bool SIG = kSigmaOnly<Net>;
+  static_assert(!SIG || (!STORE && !BF), "the density-only pass is a render pass");
   fp.start();  // begin(0): chunk 0 landed; the barrier also publishes bias_s
 #if AON_PRIO_HALF
   if (wave >= GeomH<NCOL>::kWaves / 2) __builtin_amdgcn_s_setprio(AON_PRIO_HALF);
@@ -73,8 +87,8 @@ __device__ __forceinline__ void vanilla_layers(FP& fp, Frag<2, NCOL>& enc, Frag<
   for (int c = 0; c < NCOL && !AON_STASH_REGS; ++c)
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-      enc.hi[k][c] = __builtin_bit_cast(h8, stash[64 * enc_slot<BF>(c, k, 0)]);
-      if (!BF) enc.lo[k][c] = __builtin_bit_cast(h8, stash[64 * enc_slot<BF>(c, k, 1)]);
+      enc.hi[k][c] = __builtin_bit_cast(h8, stash[64 * enc_slot<BF, SIG>(c, k, 0)]);
+      if (!BF) enc.lo[k][c] = __builtin_bit_cast(h8, stash[64 * enc_slot<BF, SIG>(c, k, 1)]);
     }
   // skip: cat[h, enc] (model.py:102-103)
   layer_h<Net, L5, true>(fp, x, enc, y, bias_l, g, SP::make(th + 5 * hs, 256, rows, N, g, ts.masks + 5 * ms));
@@ -84,22 +98,24 @@ __device__ __forceinline__ void vanilla_layers(FP& fp, Frag<2, NCOL>& enc, Frag<
   head_h<Net, LDEN>(fp, y, dens, bias_l, g);             // model.py:105-107
   constexpr bool FOLD = std::is_same<Net, NetVanillaFoldH>::value;
   static_assert(!FOLD || !STORE, "the training forwards keep the bottleneck activation");
-  // bottleneck, no activation (model.py:109) -- the render stream has none: it is folded into
-  // the view layer's weights (mlp_layout.hpp kLayersHFold), which then reads h7 (y) itself
-  if constexpr (!FOLD)
-    layer_h<Net, LBOT, false>(fp, y, none, x, bias_l, g, SP::make(tbot, 256, rows, N, g));
+  if constexpr (!SIG) {  // (the density-only pass: its stream ends with the density head)
+    // bottleneck, no activation (model.py:109) -- the render stream has none: it is folded into
+    // the view layer's weights (mlp_layout.hpp kLayersHFold), which then reads h7 (y) itself
+    if constexpr (!FOLD)
+      layer_h<Net, LBOT, false>(fp, y, none, x, bias_l, g, SP::make(tbot, 256, rows, N, g));
 #pragma unroll
-  for (int c = 0; c < NCOL && !AON_STASH_REGS; ++c) {
-    venc.hi[0][c] = __builtin_bit_cast(h8, stash[64 * venc_slot<BF>(c, 0)]);
-    if (!BF) venc.lo[0][c] = __builtin_bit_cast(h8, stash[64 * venc_slot<BF>(c, 1)]);
-  }
-  // cat[bottleneck, enc_dir] + ReLU (:110-116), rgb head (:118)
-  if constexpr (FOLD) {
-    layer_h<Net, LF_VIEW, true>(fp, y, venc, x, bias_l, g);
-    head_h<Net, LF_RGB>(fp, x, rgb, bias_l, g);
-  } else {
-    layer_h<Net, LVIEW, true>(fp, x, venc, y, bias_l, g, SP::make(thv, 128, rows, N, g, ts.masks + 8 * ms));
-    head_h<Net, LRGB>(fp, y, rgb, bias_l, g);
+    for (int c = 0; c < NCOL && !AON_STASH_REGS; ++c) {
+      venc.hi[0][c] = __builtin_bit_cast(h8, stash[64 * venc_slot<BF>(c, 0)]);
+      if (!BF) venc.lo[0][c] = __builtin_bit_cast(h8, stash[64 * venc_slot<BF>(c, 1)]);
+    }
+    // cat[bottleneck, enc_dir] + ReLU (:110-116), rgb head (:118)
+    if constexpr (FOLD) {
+      layer_h<Net, LF_VIEW, true>(fp, y, venc, x, bias_l, g);
+      head_h<Net, LF_RGB>(fp, x, rgb, bias_l, g);
+    } else {
+      layer_h<Net, LVIEW, true>(fp, x, venc, y, bias_l, g, SP::make(thv, 128, rows, N, g, ts.masks + 8 * ms));
+      head_h<Net, LRGB>(fp, y, rgb, bias_l, g);
+    }
   }
 
   if (g == 0) {
@@ -109,8 +125,12 @@ __device__ __forceinline__ void vanilla_layers(FP& fp, Frag<2, NCOL>& enc, Frag<
         const float s = AON_F16X3_V2 ? 1.0f : 1.0f / kActScale;  // V2 heads are at true scale
         float sig = dens[c][0] * s;
         if (STORE && ts.noise) sig = __fadd_rn(sig, ts.noise[rows[c]]);  // raw_sigma + noise
-        const f4 o = {act_rgb(rgb[c][0] * s, act), act_rgb(rgb[c][1] * s, act),
-                      act_rgb(rgb[c][2] * s, act), act_sigma(sig, act)};
+        f4 o = {0.0f, 0.0f, 0.0f, act_sigma(sig, act)};  // density-only: no colour
+        if constexpr (!SIG) {
+          o[0] = act_rgb(rgb[c][0] * s, act);
+          o[1] = act_rgb(rgb[c][1] * s, act);
+          o[2] = act_rgb(rgb[c][2] * s, act);
+        }
 #ifdef AON_ABL_NO_RAW_STORE  // timing-only A/B build (fused-pipeline question): no raw store
         if (__builtin_isnan(o[0] + o[1] + o[2] + o[3]))
 #endif
@@ -120,19 +140,25 @@ __device__ __forceinline__ void vanilla_layers(FP& fp, Frag<2, NCOL>& enc, Frag<
   }
 }
 
-// MODE 0: (rays_o, rays_d, viewdirs, t) inputs; MODE 1: encoded x (N, 63), condition (B, 27).
+// MODE 0: (rays_o, rays_d, viewdirs, t) inputs; MODE 1: encoded x (N, 63), condition (B, 27);
+// MODE 2: (rays_o, rays_d, condition (B, 27), t) -- the position encoding in registers as in
+// MODE 0, the per-ray view encoding read as in MODE 1 instead of 8 sines per lane and tile.
 // BF: bf16 numerics (one bf16 MFMA per k-step; the kept activations stored as bf16) -- the
 // bf16 training mode; the stream then carries bf16 weights in its hi blocks (k_pack_h bf16).
 // Net: the stream's layer table -- NetVanillaFoldH for the render (no bottleneck layer),
-// NetVanillaH for the training forwards (STORE).
+// NetVanillaH for the training forwards (STORE), NetVanillaSigmaH for the density-only render
+// pass (MODE 0 inputs without viewdirs: no view encoding is formed, split or stashed; the bias
+// table and the status word are the whole render stream's, bias_g / status).
 template <int MODE, int NCOL, bool STORE = false, bool BF = false, typename Net = NetVanillaH>
 __global__ __launch_bounds__((GeomH<NCOL, BF>::kThreads), (GeomH<NCOL, BF>::kWavesPerSimd)) void k_mlp_fwd_f16x3(
     const f4* __restrict__ wstream, const float* __restrict__ bias_g, const float* __restrict__ in0,
     const float* __restrict__ in1, const float* __restrict__ in2, const float* __restrict__ in3,
     int64_t B, int S, int act, float* __restrict__ raw, TrainStore ts = {}) {
   using G = GeomH<NCOL, BF>;
+  constexpr bool SIG = kSigmaOnly<Net>;
+  static_assert(!SIG || MODE == 0, "the density-only pass takes MODE 0 inputs");
   // ONE __shared__ object: weight ring | bias table | per-lane stash of the encodings
-  constexpr int kPer = stash_per<BF>() * NCOL;  // f4 per lane: enc 2 k-steps + venc 1, hi (& lo)
+  constexpr int kPer = stash_per<BF, SIG>() * NCOL;  // f4 per lane: enc 2 k-steps + venc 1, hi (& lo)
   constexpr int kStash = AON_STASH_REGS ? 0 : G::kWaves * 64 * kPer;
   static_assert((kLdsWeights + Net::kBiasFloats / 4 + kStash) * 16 <= 160 * 1024, "LDS");
   __shared__ f4 smem[kLdsWeights + Net::kBiasFloats / 4 + kStash];
@@ -164,7 +190,7 @@ __global__ __launch_bounds__((GeomH<NCOL, BF>::kThreads), (GeomH<NCOL, BF>::kWav
     const int64_t rr = row < N ? row : N - 1;
     const int64_t ray = rr / S;
     float ev[2][8], vv[8];
-    if (MODE == 0) {
+    if constexpr (MODE == 0 && !SIG) {
       const float* ro = in0 + 3 * ray;
       const float* rd = in1 + 3 * ray;
       const float* vd = in2 + 3 * ray;
@@ -193,6 +219,37 @@ __global__ __launch_bounds__((GeomH<NCOL, BF>::kThreads), (GeomH<NCOL, BF>::kWav
         encode(std::true_type{});
       else
         encode(std::false_type{});
+    } else if constexpr (MODE == 0 || MODE == 2) {
+      // the density-only pass, or MODE 2: pos_enc(x) as above, no sine of the view direction
+      const float* ro = in0 + 3 * ray;
+      const float* rd = in1 + 3 * ray;
+      const float tt = in3[rr];
+      const float x0 = __fadd_rn(ro[0], __fmul_rn(tt, rd[0]));
+      const float x1 = __fadd_rn(ro[1], __fmul_rn(tt, rd[1]));
+      const float x2 = __fadd_rn(ro[2], __fmul_rn(tt, rd[2]));
+      auto encode = [&](auto fast) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+#pragma unroll
+          for (int e = 0; e < 8; ++e)
+          {
+            ev[k][e] = pos_enc_feature_fast(x0, x1, x2, 32 * k + 8 * g + e, 0, 10, fast.value);
+            __builtin_amdgcn_sched_barrier(0);  // one feature's fp64 temporaries live at a time
+          }
+      };
+      // (fast or not, a feature is the same value bit for bit: aon_common.hpp)
+      if (pos_enc_fast_ok(x0, x1, x2, 10))
+        encode(std::true_type{});
+      else
+        encode(std::false_type{});
+      if constexpr (MODE == 2) {
+        const float* cd = in2 + ray * 27;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const int f = 8 * g + e;
+          vv[e] = f < 27 ? cd[f] : 0.f;
+        }
+      }
     } else {
       const float* x = in0 + rr * 63;
       const float* cd = in1 + ray * 27;
@@ -216,9 +273,11 @@ __global__ __launch_bounds__((GeomH<NCOL, BF>::kThreads), (GeomH<NCOL, BF>::kWav
       for (int e = 0; e < 8; ++e) ev[k][e] *= act_scale<BF>();
       split8<BF>(ev[k], enc.hi[k][c], enc.lo[k][c], enc.ovf);
     }
+    if constexpr (!SIG) {
 #pragma unroll
-    for (int e = 0; e < 8; ++e) vv[e] *= act_scale<BF>();
-    split8<BF>(vv, venc.hi[0][c], venc.lo[0][c], venc.ovf);
+      for (int e = 0; e < 8; ++e) vv[e] *= act_scale<BF>();
+      split8<BF>(vv, venc.hi[0][c], venc.lo[0][c], venc.ovf);
+    }
   }
 
   // park the encodings in LDS until the skip / view layers need them (frees 24 VGPRs for the
@@ -227,11 +286,13 @@ __global__ __launch_bounds__((GeomH<NCOL, BF>::kThreads), (GeomH<NCOL, BF>::kWav
   for (int c = 0; c < NCOL && !AON_STASH_REGS; ++c) {
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-      stash[64 * enc_slot<BF>(c, k, 0)] = __builtin_bit_cast(f4, enc.hi[k][c]);
-      if (!BF) stash[64 * enc_slot<BF>(c, k, 1)] = __builtin_bit_cast(f4, enc.lo[k][c]);
+      stash[64 * enc_slot<BF, SIG>(c, k, 0)] = __builtin_bit_cast(f4, enc.hi[k][c]);
+      if (!BF) stash[64 * enc_slot<BF, SIG>(c, k, 1)] = __builtin_bit_cast(f4, enc.lo[k][c]);
     }
-    stash[64 * venc_slot<BF>(c, 0)] = __builtin_bit_cast(f4, venc.hi[0][c]);
-    if (!BF) stash[64 * venc_slot<BF>(c, 1)] = __builtin_bit_cast(f4, venc.lo[0][c]);
+    if constexpr (!SIG) {
+      stash[64 * venc_slot<BF>(c, 0)] = __builtin_bit_cast(f4, venc.hi[0][c]);
+      if (!BF) stash[64 * venc_slot<BF>(c, 1)] = __builtin_bit_cast(f4, venc.lo[0][c]);
+    }
   }
 
   Frag<8, NCOL> x, y;
@@ -246,7 +307,10 @@ __global__ __launch_bounds__((GeomH<NCOL, BF>::kThreads), (GeomH<NCOL, BF>::kWav
     FragPipe<WP, AON_PREFETCH, 0, BF> fp(p);
     vanilla_layers<Net, NCOL, STORE, T>(fp, enc, venc, x, y, stash, bias_s, g, wave, rows, N, act, raw, ts);
   }
-  range_report(bias_g + Net::kBiasFloats, ovf_of(x) | ovf_of(y) | enc.ovf | venc.ovf);
+  // every split of this launch: the layers' (x, y) and the encodings' (venc.ovf stays 0 in the
+  // density-only pass, which splits none); the status word sits behind the WHOLE bias table
+  constexpr int kStatusAt = SIG ? NetVanillaFoldH::kBiasFloats : Net::kBiasFloats;
+  range_report(bias_g + kStatusAt, ovf_of(x) | ovf_of(y) | enc.ovf | venc.ovf);
 }
 
 // ---- packing: torch [out][ldw] fp32 -> hi/lo fp16 blocks (+ biases at activation scale), for
@@ -443,6 +507,35 @@ int launch_f16x3(int mode, int ncol, const void* packed, const float* a0, const 
   else AON_LAUNCH_H(1, 2);
 #undef AON_LAUNCH_H
   return launch_status("aon_mlp_fwd");
+}
+
+// the render stream's bias table (and, behind it, the status word)
+static const float* fold_bias(const void* packed) {
+  return reinterpret_cast<const float*>(static_cast<const char*>(packed) +
+                                        NetVanillaFoldH::kStreamBytes);
+}
+
+int launch_f16x3_sigma(const void* packed, const float* rays_o, const float* rays_d,
+                       const float* t, int64_t B, int S, int act, float* raw, hipStream_t stream) {
+  using G = GeomH<1>;
+  const int64_t N = B * S;
+  hipLaunchKernelGGL((k_mlp_fwd_f16x3<0, 1, false, false, NetVanillaSigmaH>),
+                     static_cast<int>((N + G::kRowsPerBlock - 1) / G::kRowsPerBlock), G::kThreads, 0,
+                     stream, static_cast<const f4*>(packed), fold_bias(packed), rays_o, rays_d,
+                     static_cast<const float*>(nullptr), t, B, S, act, raw);
+  return launch_status("aon_mlp_fwd_sigma");
+}
+
+int launch_f16x3_cond(const void* packed, const float* rays_o, const float* rays_d,
+                      const float* cond, const float* t, int64_t B, int S, int act, float* raw,
+                      hipStream_t stream) {
+  using G = GeomH<1>;
+  const int64_t N = B * S;
+  hipLaunchKernelGGL((k_mlp_fwd_f16x3<2, 1, false, false, NetVanillaFoldH>),
+                     static_cast<int>((N + G::kRowsPerBlock - 1) / G::kRowsPerBlock), G::kThreads, 0,
+                     stream, static_cast<const f4*>(packed), fold_bias(packed), rays_o, rays_d, cond,
+                     t, B, S, act, raw);
+  return launch_status("aon_mlp_fwd_cond");
 }
 
 }  // namespace mlp

@@ -275,6 +275,42 @@ constexpr bool layout_fold_ok() {
          kBiasFloatsFold == kBiasFloats - b.u * 16;
 }
 static_assert(layout_fold_ok(), "folded layout must be kLayersH without the bottleneck");
+
+// The density-only render pass (aon_mlp_fwd_sigma: the coarse level of a render that keeps only
+// the fine level's colour -- its rgb reaches nothing, its sigma the fine level's samples): the
+// trunk and the density head, the first LDEN + 1 layers of kLayersHFold.  The density head is
+// consumed before the view layer, so the pass reads a PREFIX of the packed render stream, in
+// place: same buffer, same bias table and status word (behind the whole stream's
+// NetVanillaFoldH::kStreamBytes, not behind the prefix).  The prefix's 1,936 blocks round up to
+// whole ring chunks of 32 (the ring then copies 16 of the view layer's blocks, never read); only
+// the prefix's rows of the bias table are staged in LDS.
+constexpr int kNumLayersSigma = LDEN + 1;
+constexpr int kBlocksSigma = 1936;
+constexpr int kStreamBlocksSigma = (kBlocksSigma + 31) / 32 * 32;  // 1952
+constexpr int kBiasFloatsSigma = 2064;
+struct NetVanillaSigmaH
+    : NetH<kLayersHFold, kNumLayersSigma, kBlocksSigma, kStreamBlocksSigma, kBiasFloatsSigma> {};
+// the prefix matches the folded stream block for block and bias offset for bias offset: the
+// table is the same array, and the prefix ends where the view layer begins
+constexpr bool layout_sigma_ok() {
+  int blk = 0, bias = 0;
+  for (int i = 0; i < kNumLayersSigma; ++i) {
+    const LayerDesc s = NetVanillaSigmaH::layer(i);
+    const LayerDesc& f = kLayersHFold[i];
+    if (s.ka != f.ka || s.kb != f.kb || s.u != f.u || s.len_a != f.len_a || s.len_b != f.len_b ||
+        s.out_real != f.out_real || s.blk0 != f.blk0 || s.bias0 != f.bias0)
+      return false;
+    if (f.blk0 != blk || f.bias0 != bias) return false;
+    blk += (f.ka + f.kb) * f.u * 2;
+    bias += f.u * 16;
+  }
+  return blk == kBlocksSigma && bias == kBiasFloatsSigma &&
+         kLayersHFold[LF_VIEW].blk0 == kBlocksSigma &&
+         kLayersHFold[LF_VIEW].bias0 == kBiasFloatsSigma &&
+         kBiasFloatsSigma % 4 == 0 && kStreamBlocksSigma >= kBlocksSigma &&
+         kStreamBlocksSigma <= kStreamBlocksFold;
+}
+static_assert(layout_sigma_ok(), "the density-only pass must be a prefix of the folded stream");
 static_assert(NetArtH::ok(), "inconsistent articulated fp16x3 layout");
 static_assert(NetBwdH::ok(), "inconsistent backward-chain fp16x3 layout");
 static_assert(NetArtBwdH::ok(), "inconsistent articulated backward-chain fp16x3 layout");
@@ -407,6 +443,14 @@ int absmax(const float* x, int64_t n, uint32_t* out, hipStream_t stream);
 int launch_f16x3(int mode, int ncol, const void* packed, const float* a0, const float* a1,
                  const float* a2, const float* a3, int64_t B, int S, int act, float* raw,
                  hipStream_t stream, const TrainStore* ts = nullptr);
+// the render stream's two-pass entry points (16 samples per wave): the density-only pass
+// (NetVanillaSigmaH: raw rows {0, 0, 0, sigma}) and the conditioned forward (kernel MODE 2: the
+// view encodings from a (B, 27) table) -- column 3 / all of launch_f16x3 mode 0, bit for bit
+int launch_f16x3_sigma(const void* packed, const float* rays_o, const float* rays_d,
+                       const float* t, int64_t B, int S, int act, float* raw, hipStream_t stream);
+int launch_f16x3_cond(const void* packed, const float* rays_o, const float* rays_d,
+                      const float* cond, const float* t, int64_t B, int S, int act, float* raw,
+                      hipStream_t stream);
 // the weight-streamed fp16x3 render forward (mlp_ws.hip; MODE 0 inputs, bit-identical to
 // launch_f16x3 mode 0) -- an A/B variant, not in the release library: `make variant-ws` builds
 // lib/variants/libaonerf_ws.so with AON_DATAFLOW_WS_BUILD = 1, whose render forwards

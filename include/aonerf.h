@@ -213,6 +213,28 @@ int aon_mlp_fwd_encoded(const void* packed, int precision, const float* x,
                         const float* condition, int64_t B, int S, int act, float* out,
                         aon_stream_t stream);
 
+/* A render that keeps only the fine level's colour, in two passes over AON_PREC_F16X3 packs (the
+ * render stream; additive in ABI 13).  Both refuse AON_PREC_F16X3_TRAIN, AON_PREC_BF16 and
+ * AON_PREC_FP32 (a fp32 pack renders with aon_mlp_fwd), NULL pointers and misaligned packed / out
+ * before any launch; neither allocates nor synchronises (graph-capturable, as aon_mlp_fwd).
+ *
+ * aon_mlp_fwd_sigma: the density-only pass.  The coarse level reaches such a frame only through
+ * aon_composite_march's weights, which read sigma and t: this runs the trunk and the density
+ * head -- a prefix of the packed stream, read in place -- and no view layer, rgb head or view
+ * encoding.  out (B*S, 4) = [0, 0, 0, sigma]: column 3 is aon_mlp_fwd's column 3 bit for bit
+ * (act as there), columns 0..2 are 0.  The range guard reports through the pack's status word
+ * as aon_mlp_fwd does, for the values this pass splits (an overflow confined to the view layer
+ * is not one of them). */
+int aon_mlp_fwd_sigma(const void* packed, int precision, const float* rays_o, const float* rays_d,
+                      const float* t, int64_t B, int S, int act, float* out, aon_stream_t stream);
+
+/* aon_mlp_fwd_cond: aon_mlp_fwd with the per-ray view encoding given, not recomputed per sample:
+ * cond (B, 27) = pos_enc(viewdirs, 0, 4), e.g. from aon_pos_enc.  With that table out equals
+ * aon_mlp_fwd's bit for bit. */
+int aon_mlp_fwd_cond(const void* packed, int precision, const float* rays_o, const float* rays_d,
+                     const float* cond, const float* t, int64_t B, int S, int act, float* out,
+                     aon_stream_t stream);
+
 /* Kept tensors of the fused training kernels (activations, ReLU' bits, the backward chains'
  * pre-activation gradients) are stored TILED, in contiguous row-major 16 x 16 tiles (one MFMA
  * output fragment each): for N rows of width W (a multiple of 16), element (row, f) at

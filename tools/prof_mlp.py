@@ -1,6 +1,10 @@
 """Run the fused MLP kernel alone (one launch per precision) for counter collection / timing.
 
     python tools/prof_mlp.py [--rows N] [--precision f16x3|fp32|all] [--reps R]
+                             [--entry full|sigma|cond]
+
+--entry (f16x3): aon_mlp_fwd (full), the density-only pass aon_mlp_fwd_sigma, or aon_mlp_fwd_cond
+on the view encodings of the same directions (the two-pass render's coarse / fine launches).
 """
 import argparse
 import os
@@ -22,6 +26,7 @@ ap.add_argument("--rays", type=int, default=307200 // 4)
 ap.add_argument("--samples", type=int, default=193)
 ap.add_argument("--precision", default="all")
 ap.add_argument("--reps", type=int, default=3)
+ap.add_argument("--entry", default="full", choices=["full", "sigma", "cond"])
 ap.add_argument("--dump", default="", help="write the last raw output's sha256 here (A/B bit-identity)")
 a = ap.parse_args()
 g = torch.Generator(device="cuda").manual_seed(0)
@@ -31,12 +36,21 @@ d = torch.nn.functional.normalize(torch.randn(B, 3, device="cuda", generator=g),
 t = torch.sort(torch.rand(B, S, device="cuda", generator=g) * 4 + 2, dim=-1).values
 net = init_like_reference(NeRF()).cuda()
 precs = ["fp32", "f16x3"] if a.precision == "all" else [a.precision]
+if a.entry != "full":
+    precs = ["f16x3"]  # the two-pass entry points take the f16x3 render stream only
+if a.entry == "cond":
+    from aonerf import helper  # noqa: E402
+
+    cond = helper.pos_enc(d, 0, 4)
 for p in precs:
     net.set_precision(p)
     for _ in range(a.reps):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        raw = net.fine_mlp.forward_rays(o, d, d, t)
+        if a.entry == "sigma":
+            raw = net.fine_mlp.forward_sigma(o, d, t)
+        else:
+            raw = net.fine_mlp.forward_rays(o, d, d, t, **({"cond": cond} if a.entry == "cond" else {}))
         e1.record()
         torch.cuda.synchronize()
         ms = e0.elapsed_time(e1)

@@ -163,6 +163,15 @@ _SIGNATURES = {
     "aon_get_rays": (c_int, [vp, c_i64, vp, vp, vp, vp, c_int, c_int, vp, vp]),
     "aon_frame_rays": (c_int, [c_int, c_int, c_float, vp, c_i64, c_i64, vp, vp, vp, vp]),
     "aon_sample_along_rays": (c_int, [vp, vp, c_i64, c_int, vp, vp, vp, vp, vp, vp]),
+    "aon_ray_limits_box": (c_int, [vp, vp, c_i64, c_float, vp, vp, vp]),
+    "aon_ray_limits_workspace_bytes": (c_size, [c_i64]),
+    "aon_ray_limits": (c_int, [vp, vp, c_i64, c_float, vp, vp, vp, c_size, vp]),
+    "aon_sample_along_rays_bounds": (c_int, [vp, vp, c_i64, c_int, vp, vp, vp, c_int, vp, vp, vp,
+                                             vp]),
+    "aon_compact_rays_workspace_bytes": (c_size, [c_i64]),
+    "aon_compact_rays": (c_int, [vp, vp, vp, vp, vp, c_i64, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                 c_size, vp]),
+    "aon_scatter_payload": (c_int, [vp, vp, vp, c_i64, vp, c_i64, c_int, vp, vp]),
     "aon_pos_enc": (c_int, [vp, c_i64, c_int, c_int, vp, vp]),
     "aon_sample_rays": (c_int, [vp, vp, c_int, c_i64, c_int, c_int, c_float, vp, c_i64, c_int,
                                 c_float, vp, vp, vp, vp, vp]),

@@ -59,23 +59,133 @@ def eval_u(num_samples, device, float_min_eps=2 ** -32):
     return _sched_cache[key]
 
 
+def unit_schedule(num_samples, device):
+    """torch.linspace(0, 1, num_samples + 1) of helper.py:116 as a device tensor (built on the
+    CPU, as the reference's values are)."""
+    key = ("s", int(num_samples), str(device))
+    if key not in _sched_cache:
+        _sched_cache[key] = torch.linspace(0.0, 1.0, num_samples + 1).to(device)
+    return _sched_cache[key]
+
+
+# ----------------------------------------------------------------------------- box bounds
+def _flat_rays(rays_o, rays_d, box_side_length):
+    L.require_gpu(rays_o, rays_d)
+    if rays_o.shape[-1] != 3 or rays_o.shape != rays_d.shape:
+        raise ValueError("ray limits expect rays_o and rays_d of one shape (..., 3)")
+    half = float(box_side_length / 2)
+    o = L.contig(rays_o.detach().reshape(-1, 3))
+    d = L.contig(rays_d.detach().reshape(-1, 3))
+    return o, d, half, tuple(rays_o.shape[:-1]) + (1,)
+
+
+def get_ray_limits_box(rays_o, rays_d, box_side_length):
+    """reference helper.py:42-102 -> (tmin, tmax), each (..., 1); misses hold (-1, -2)."""
+    o, d, half, shape = _flat_rays(rays_o, rays_d, box_side_length)
+    B = o.shape[0]
+    tmin, tmax = torch.empty((B,), device=o.device), torch.empty((B,), device=o.device)
+    L.call("aon_ray_limits_box", L.ptr(o), L.ptr(d), B, half, L.ptr(tmin), L.ptr(tmax),
+           L.stream(o.device))
+    return tmin.reshape(shape), tmax.reshape(shape)
+
+
+def get_ray_limits(rays_o, rays_d, box_side_length=2):
+    """reference helper.py:29-39 -> (near, far), each (..., 1): the box limits, the rays that
+    miss filled with the batch's smallest near / largest far, negatives clamped to 0."""
+    o, d, half, shape = _flat_rays(rays_o, rays_d, box_side_length)
+    B = o.shape[0]
+    near, far = torch.empty((B,), device=o.device), torch.empty((B,), device=o.device)
+    nbytes = L.lib().aon_ray_limits_workspace_bytes(B)
+    work = torch.empty((nbytes // 4,), dtype=torch.int32, device=o.device)
+    L.call("aon_ray_limits", L.ptr(o), L.ptr(d), B, half, L.ptr(near), L.ptr(far), L.ptr(work),
+           nbytes, L.stream(o.device))
+    return near.reshape(shape), far.reshape(shape)
+
+
+def compact_rays(tmin, tmax, rays_o, rays_d, viewdirs=None):
+    """The rays that hit the box (tmax > max(tmin, 0); NaN: a miss), in order, from the box
+    limits of get_ray_limits_box.  Returns a dict: ``slot`` (B,) int32 -- the rank of each ray
+    among the hits or -1; ``n_hit`` -- a 0-dim int32 DEVICE tensor (reading it is the caller's
+    one sync); and, B rows each of which the first n_hit are written, ``idx`` (int32),
+    ``rays_o`` / ``rays_d`` / ``viewdirs`` (B, 3), ``near`` = max(tmin, 0) and ``far`` (B,)."""
+    L.require_gpu(tmin, tmax, rays_o, rays_d, viewdirs)
+    B = rays_o.shape[0]
+    dev = rays_o.device
+    if tmin.numel() != B or tmax.numel() != B:
+        raise ValueError(f"tmin / tmax must hold {B} limits")
+    tmin, tmax = L.contig(tmin.reshape(B)), L.contig(tmax.reshape(B))
+    rays_o, rays_d = L.contig(rays_o), L.contig(rays_d)
+    viewdirs = None if viewdirs is None else L.contig(viewdirs)
+    out = {"slot": torch.empty((B,), dtype=torch.int32, device=dev),
+           "idx": torch.empty((B,), dtype=torch.int32, device=dev),
+           "rays_o": torch.empty((B, 3), device=dev), "rays_d": torch.empty((B, 3), device=dev),
+           "viewdirs": None if viewdirs is None else torch.empty((B, 3), device=dev),
+           "near": torch.empty((B,), device=dev), "far": torch.empty((B,), device=dev),
+           "n_hit": torch.empty((), dtype=torch.int32, device=dev)}
+    nbytes = L.lib().aon_compact_rays_workspace_bytes(B)
+    work = torch.empty((nbytes // 4,), dtype=torch.int32, device=dev)
+    L.call("aon_compact_rays", L.ptr(tmin), L.ptr(tmax), L.ptr(rays_o), L.ptr(rays_d),
+           L.ptr(viewdirs), B, L.ptr(out["slot"]), L.ptr(out["idx"]), L.ptr(out["rays_o"]),
+           L.ptr(out["rays_d"]), L.ptr(out["viewdirs"]), L.ptr(out["near"]), L.ptr(out["far"]),
+           L.ptr(out["n_hit"]), L.ptr(work), nbytes, L.stream(dev))
+    return out
+
+
+def scatter_payload(comp, acc, depth, slot, white_bkgd):
+    """(B, 5) = [rgb(3), depth, acc] per frame ray from the rendered compact rows (comp (n, 3),
+    acc / depth (n,)): row slot[b], or the background row (rgb 1 or 0, depth 0, acc 0)."""
+    L.require_gpu(comp, acc, depth)
+    B, n = slot.shape[0], comp.shape[0]
+    if slot.dtype != torch.int32 or tuple(comp.shape) != (n, 3) or acc.numel() != n \
+            or depth.numel() != n:
+        raise ValueError("scatter_payload: slot must be int32, comp (n, 3), acc / depth (n,)")
+    comp, acc, depth, slot = (L.contig(x) for x in (comp, acc, depth, slot))
+    out = torch.empty((B, 5), device=slot.device)
+    L.call("aon_scatter_payload", L.ptr(comp), L.ptr(acc), L.ptr(depth), n, L.ptr(slot), B,
+           int(bool(white_bkgd)), L.ptr(out), L.stream(slot.device))
+    return out
+
+
 # ----------------------------------------------------------------------------- sampling
+def _ray_bound(x, B, dev, name):
+    """A per-ray bound as a contiguous (B,) device tensor: (B,), (B, 1), or a python number."""
+    if not isinstance(x, torch.Tensor):
+        return torch.full((B,), x, dtype=torch.float32, device=dev)
+    L.require_gpu(x)
+    if tuple(x.shape) not in ((B,), (B, 1)):
+        raise ValueError(f"{name} must be a number or a ({B},) / ({B}, 1) tensor, got "
+                         f"{tuple(x.shape)}")
+    return L.contig(x.detach().reshape(B))
+
+
 def sample_along_rays(rays_o, rays_d, num_samples, near, far, randomized, lindisp, *, u=None,
                       want_coords=True):
-    """reference helper.py:106-133 -> (t_vals (B, S+1), coords (B, S+1, 3))."""
+    """reference helper.py:106-133 -> (t_vals (B, S+1), coords (B, S+1, 3)).  ``near`` / ``far``:
+    two python numbers (one cached schedule for the batch), or per-ray bounds -- a (B,) or
+    (B, 1) tensor for either, the other a tensor or a number (helper.py:117-120 broadcasting)."""
     L.require_gpu(rays_o, rays_d, u)
     rays_o, rays_d = L.contig(rays_o), L.contig(rays_d)
     B, S = rays_o.shape[0], num_samples + 1
     dev = rays_o.device
-    t_sched, lower, upper = coarse_schedule(num_samples, near, far, lindisp, dev)
+    per_ray = isinstance(near, torch.Tensor) or isinstance(far, torch.Tensor)
+    if per_ray:
+        near, far = _ray_bound(near, B, dev, "near"), _ray_bound(far, B, dev, "far")
+        s_tab = unit_schedule(num_samples, dev)
+    else:
+        t_sched, lower, upper = coarse_schedule(num_samples, near, far, lindisp, dev)
     if randomized and u is None:
         u = torch.rand((B, S), device=dev)
     u = L.contig(u) if randomized else None
-    base = lower if randomized else t_sched  # eval mode: the schedule itself (helper.py:129)
     if u is not None and tuple(u.shape) != (B, S):
         raise ValueError(f"u must be ({B}, {S})")
     t_vals = torch.empty((B, S), device=dev)
     coords = torch.empty((B, S, 3), device=dev) if want_coords else None
+    if per_ray:
+        L.call("aon_sample_along_rays_bounds", L.ptr(rays_o), L.ptr(rays_d), B, S, L.ptr(s_tab),
+               L.ptr(near), L.ptr(far), int(bool(lindisp)), L.ptr(u), L.ptr(t_vals),
+               L.ptr(coords), L.stream(dev))
+        return t_vals, coords
+    base = lower if randomized else t_sched  # eval mode: the schedule itself (helper.py:129)
     L.call("aon_sample_along_rays", L.ptr(rays_o), L.ptr(rays_d), B, S, L.ptr(base), L.ptr(upper),
            L.ptr(u), L.ptr(t_vals), L.ptr(coords), L.stream(dev))
     return t_vals, coords

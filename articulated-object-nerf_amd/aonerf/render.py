@@ -6,7 +6,7 @@ from collections import defaultdict
 import numpy as np
 import torch
 
-from . import interface
+from . import helper, interface
 from .ray_utils import frame_rays
 
 # The reference splits every image into hparams.chunk = 3840-ray pieces (opt.py:103) only to
@@ -22,11 +22,59 @@ def _chunks(B, chunk):
         yield i, min(i + chunk, B)
 
 
+def _render_box(model, rays, chunk, white_bkgd, box_side_length, cull, timers=None):
+    """(B, 5) payload [rgb(3), depth, acc] of ``rays`` bounded by the box of side
+    ``box_side_length`` around the origin.  The bounds are formed once over all the rays (the
+    fill of get_ray_limits depends on the batch), not per chunk.  ``cull``: only the rays that
+    hit the box reach the MLPs (zero hits: no MLP launch); the others are background rows."""
+    o, d, v = rays["rays_o"], rays["rays_d"], rays["viewdirs"]
+    B, dev = o.shape[0], o.device
+    if not cull:
+        near, far = helper.get_ray_limits(o, d, box_side_length)
+        out = torch.empty((B, 5), device=dev)
+        for i, j in _chunks(B, chunk):
+            sub = {k: x[i:j] for k, x in rays.items()}
+            fine = model(sub, False, white_bkgd, near[i:j], far[i:j], timers=timers,
+                         fine_only=True)[1]
+            out[i:j, 0:3] = fine[0]
+            out[i:j, 3] = fine[2]
+            out[i:j, 4] = fine[1]
+        return out
+    if torch.cuda.is_current_stream_capturing():
+        raise ValueError("box culling reads the hit count on the host, which a stream capture "
+                         "cannot record: render with cull=False under capture")
+    tmin, tmax = helper.get_ray_limits_box(o, d, box_side_length)
+    c = helper.compact_rays(tmin, tmax, o, d, v)
+    n = int(c["n_hit"].item())  # the one 4-byte read-back of the call
+    comp = torch.empty((n, 3), device=dev)
+    acc, depth = torch.empty((n,), device=dev), torch.empty((n,), device=dev)
+    for i, j in _chunks(n, chunk):
+        sub = {k: c[k][i:j] for k in ("rays_o", "rays_d", "viewdirs")}
+        fine = model(sub, False, white_bkgd, c["near"][i:j], c["far"][i:j], timers=timers,
+                     fine_only=True)[1]
+        comp[i:j], acc[i:j], depth[i:j] = fine[0], fine[1], fine[2]
+    return helper.scatter_payload(comp, acc, depth, c["slot"], white_bkgd)
+
+
 @torch.no_grad()
-def render_rays(model, batch, chunk, white_bkgd, near, far):
+def render_rays(model, batch, chunk, white_bkgd, near, far, box_side_length=None, cull=True):
     """LitNeRF.render_rays (model.py:295-321): fine-level comp_rgb/acc/depth over all rays and
-    psnr_legacy against batch['target'] (returned as 'psnr' instead of being logged)."""
+    psnr_legacy against batch['target'] (returned as 'psnr' instead of being logged).
+
+    ``box_side_length`` (default None: ``near`` / ``far`` as given): bound every ray by the box
+    of that side around the origin instead (helper.get_ray_limits; ``near`` / ``far`` are then
+    unused).  With ``cull`` the rays that miss the box skip both MLPs and come out as background
+    (rgb 1 or 0 by ``white_bkgd``, acc 0, depth 0): one 4-byte read-back per call, so not under
+    stream capture (``cull=False`` there)."""
     B = batch["rays_o"].shape[0]
+    if box_side_length is not None:
+        rays = {k: batch[k] for k in ("rays_o", "rays_d", "viewdirs")}
+        p = _render_box(model, rays, chunk, white_bkgd, box_side_length, cull)
+        out = {"comp_rgb": p[:, 0:3].contiguous(), "acc": p[:, 4].contiguous(),
+               "depth": p[:, 3].contiguous()}
+        if "target" in batch:
+            out["psnr"] = interface.psnr_legacy(out["comp_rgb"], batch["target"]).mean()
+        return out
     ret = defaultdict(list)
     for i, j in _chunks(B, chunk):
         sub = {k: batch[k][i:j] for k in ("rays_o", "rays_d", "viewdirs")}
@@ -54,11 +102,14 @@ def render_rays_test(model, batch, chunk, white_bkgd, near, far):
 
 @torch.no_grad()
 def render_frame(model, c2w, H, W, focal, near=2.0, far=6.0, white_bkgd=True, p0=0, n=None,
-                 chunk=None, timers=None):
+                 chunk=None, timers=None, box_side_length=None, cull=True):
     """Fused ray generation + two-level render of pixels [p0, p0+n) of an H x W frame.
-    Returns (n, 5) = [rgb(3), depth, acc] per pixel (the payload of the frame gather)."""
+    Returns (n, 5) = [rgb(3), depth, acc] per pixel (the payload of the frame gather).
+    ``box_side_length`` / ``cull``: as render_rays (the bounds are formed over the n pixels)."""
     n = H * W - p0 if n is None else n
     rays = frame_rays(c2w, H, W, focal, p0, n)
+    if box_side_length is not None:
+        return _render_box(model, rays, chunk, white_bkgd, box_side_length, cull, timers)
     out = torch.empty((n, 5), device=rays["rays_o"].device)
     for i, j in _chunks(n, chunk):
         sub = {k: v[i:j] for k, v in rays.items()}

@@ -30,7 +30,10 @@ typedef void* aon_stream_t; /* hipStream_t */
                             * Added since, without a version change (purely additive):
                             * aon_ssim_workspace_bytes, aon_image_ssim, aon_ssim_tile,
                             * aon_loss_masked, aon_loss_masked_bwd; AON_PREC_F16X3_TRAIN (the
-                            * AON_PREC_F16X3 stream now has bottleneck_layer folded in) */
+                            * AON_PREC_F16X3 stream now has bottleneck_layer folded in);
+                            * aon_ray_limits_box, aon_ray_limits, aon_sample_along_rays_bounds,
+                            * aon_compact_rays, aon_scatter_payload and their workspace
+                            * queries */
 
 /* Precision of the MLP GEMMs (see DESIGN.md "MLP precision modes"). */
 #define AON_PREC_FP32 0  /* exact fp32 MFMA (v_mfma_f32_16x16x4_f32) */
@@ -85,6 +88,63 @@ int aon_frame_rays(int H, int W, float focal, const float* c2w_host, int64_t p0,
 int aon_sample_along_rays(const float* rays_o, const float* rays_d, int64_t B, int S,
                           const float* t_lower, const float* t_upper, const float* u,
                           float* t_out, float* xyz_out, aon_stream_t stream);
+
+/* ---------------------------------------------------------------- box bounds */
+/* get_ray_limits_box (models/vanilla_nerf/helper.py:42-102): the slab test of B rays against
+ * the axis-aligned box [-half_side, half_side]^3, half_side = (float)(box_side_length / 2)
+ * formed by the caller.  Bit for bit the reference's torch CPU values: invdir = 1 / d, sign =
+ * invdir < 0 (d = -0.0 selects the upper bound first), each slab (bound - o) * invdir, the
+ * reference's own comparisons (a NaN compares false) and NaN-propagating max / min; rays that
+ * miss get tmin = -1, tmax = -2.  Refused before any launch: a null pointer, B < 0 (or
+ * >= 2^31), half_side <= 0. */
+int aon_ray_limits_box(const float* rays_o, const float* rays_d, int64_t B, float half_side,
+                       float* tmin, float* tmax, aon_stream_t stream);
+
+/* get_ray_limits (helper.py:29-39): the box limits, then every ray without far > near takes
+ * the minimum near / maximum far over the rays that have it (nothing is filled when none has),
+ * then negatives become 0.  A min / max reduction: exact in any order.  work:
+ * aon_ray_limits_workspace_bytes(B) bytes, 4-byte aligned (0 from the query: B out of range).
+ * Three stream-ordered launches, no allocation, no host synchronisation. */
+size_t aon_ray_limits_workspace_bytes(int64_t B);
+int aon_ray_limits(const float* rays_o, const float* rays_d, int64_t B, float half_side,
+                   float* near, float* far, void* work, size_t work_bytes, aon_stream_t stream);
+
+/* sample_along_rays on per-ray bounds (helper.py:116-129 with (B, 1) near / far, + cast_rays
+ * :25-26).  s_tab: the S-entry torch.linspace(0, 1, S) table (built on the host: torch's CPU
+ * linspace is not a closed formula); near / far: (B,) device arrays.  One rounding per
+ * reference op: near * (1 - s) + far * s, or with lindisp 1 / (1 / near * (1 - s) + 1 / far *
+ * s); randomized iff u != NULL ((B, S)): mids = 0.5 * (t[1:] + t[:-1]), lower = [t[0], mids],
+ * upper = [mids, t[S-1]], t = lower + (upper - lower) * u.  xyz_out may be NULL.  Refused
+ * before any launch: a null pointer, B < 0, S < 2. */
+int aon_sample_along_rays_bounds(const float* rays_o, const float* rays_d, int64_t B, int S,
+                                 const float* s_tab, const float* near, const float* far,
+                                 int lindisp, const float* u, float* t_out, float* xyz_out,
+                                 aon_stream_t stream);
+
+/* Culling of the rays that miss the box -- this project's extension; the reference defines the
+ * limits (helper.py:42-102) and never culls.  A ray hits iff tmax > max(tmin, 0), comparisons
+ * with NaN false.  Order-preserving stream compaction in three stream-ordered launches without
+ * atomics (per-workgroup hit counts from wave ballots; one workgroup scans them and writes the
+ * total to *n_hit; every workgroup ranks its lanes): slot[b] = the rank of ray b among the hits
+ * or -1, for all B rays; for rank r: idx[r] = b and row r of o_out / d_out / v_out (B x 3
+ * each; viewdirs and v_out may both be NULL) holds ray b's, near_out[r] = max(tmin[b], 0),
+ * far_out[r] = tmax[b].  Every output holds B rows; rows past *n_hit are not written.  work:
+ * aon_compact_rays_workspace_bytes(B) bytes, 4-byte aligned.  No allocation and no host
+ * synchronisation inside: the caller reads *n_hit when it needs it. */
+size_t aon_compact_rays_workspace_bytes(int64_t B);
+int aon_compact_rays(const float* tmin, const float* tmax, const float* rays_o,
+                     const float* rays_d, const float* viewdirs, int64_t B, int32_t* slot,
+                     int32_t* idx, float* o_out, float* d_out, float* v_out, float* near_out,
+                     float* far_out, int32_t* n_hit, void* work, size_t work_bytes,
+                     aon_stream_t stream);
+
+/* The (B, 5) frame payload [rgb(3), depth, acc] from the n_comp rendered compact rows: ray b
+ * takes row slot[b] of comp (n_comp, 3) / depth / acc, or, with slot[b] < 0, the background
+ * row -- rgb 1 (white_bkgd) or 0, depth 0, acc 0: the density outside the box is taken to be
+ * zero (helper.py:157-195 with every weight 0).  n_comp == 0: comp / acc / depth may be NULL. */
+int aon_scatter_payload(const float* comp, const float* acc, const float* depth, int64_t n_comp,
+                        const int32_t* slot, int64_t B, int white_bkgd, float* out,
+                        aon_stream_t stream);
 
 /* Ray batches from a device-resident dataset (datasets/sapien.py:84-113, 131-154;
  * sapien_multi.py:196-238): poses (N, 3, 4) camera-to-world, images (N, H, W, C) uint8.

@@ -159,6 +159,70 @@ int main() {
   expect_invalid(aon_loss_masked_bwd(dummy, dummy, dummy, dummy, 0, dummy, nullptr, nullptr, nullptr,
                                      dummy, dummy, dummy, dummy, nullptr),
                  "loss_masked_bwd B=0");
+  // box bounds: null pointers, B < 0, S < 2 and a non-positive half_side, all before any launch
+  int32_t* ip = reinterpret_cast<int32_t*>(dummy);
+  const size_t lim_ws = aon_ray_limits_workspace_bytes(4), cmp_ws = aon_compact_rays_workspace_bytes(4);
+  expect_invalid(aon_ray_limits_box(nullptr, dummy, 4, 1.f, dummy, dummy, nullptr),
+                 "ray_limits_box null rays_o");
+  expect_invalid(aon_ray_limits_box(dummy, dummy, 4, 1.f, dummy, nullptr, nullptr),
+                 "ray_limits_box null tmax");
+  expect_invalid(aon_ray_limits_box(dummy, dummy, -1, 1.f, dummy, dummy, nullptr),
+                 "ray_limits_box B < 0");
+  expect_invalid(aon_ray_limits_box(dummy, dummy, 4, 0.f, dummy, dummy, nullptr),
+                 "ray_limits_box half_side 0");
+  expect_invalid(aon_ray_limits(dummy, nullptr, 4, 1.f, dummy, dummy, p, lim_ws, nullptr),
+                 "ray_limits null rays_d");
+  expect_invalid(aon_ray_limits(dummy, dummy, 4, 1.f, dummy, dummy, nullptr, lim_ws, nullptr),
+                 "ray_limits null work");
+  expect_invalid(aon_ray_limits(dummy, dummy, -1, 1.f, dummy, dummy, p, lim_ws, nullptr),
+                 "ray_limits B < 0");
+  expect_invalid(aon_ray_limits(dummy, dummy, 4, -1.f, dummy, dummy, p, lim_ws, nullptr),
+                 "ray_limits half_side < 0");
+  expect_invalid(aon_ray_limits(dummy, dummy, 4, 1.f, dummy, dummy, p, lim_ws - 1, nullptr),
+                 "ray_limits work_bytes too small");
+  expect_invalid(aon_sample_along_rays_bounds(dummy, dummy, 4, 8, nullptr, dummy, dummy, 0, nullptr,
+                                              dummy, nullptr, nullptr),
+                 "sample_along_rays_bounds null s_tab");
+  expect_invalid(aon_sample_along_rays_bounds(dummy, dummy, 4, 8, dummy, nullptr, dummy, 0, nullptr,
+                                              dummy, nullptr, nullptr),
+                 "sample_along_rays_bounds null near");
+  expect_invalid(aon_sample_along_rays_bounds(dummy, dummy, -1, 8, dummy, dummy, dummy, 0, nullptr,
+                                              dummy, nullptr, nullptr),
+                 "sample_along_rays_bounds B < 0");
+  expect_invalid(aon_sample_along_rays_bounds(dummy, dummy, 4, 1, dummy, dummy, dummy, 0, nullptr,
+                                              dummy, nullptr, nullptr),
+                 "sample_along_rays_bounds S < 2");
+  expect_invalid(aon_sample_along_rays_bounds(nullptr, dummy, 4, 8, dummy, dummy, dummy, 0, nullptr,
+                                              dummy, dummy, nullptr),
+                 "sample_along_rays_bounds xyz without rays_o");
+  expect_invalid(aon_compact_rays(nullptr, dummy, dummy, dummy, dummy, 4, ip, ip, dummy, dummy, dummy,
+                                  dummy, dummy, ip, p, cmp_ws, nullptr),
+                 "compact_rays null tmin");
+  expect_invalid(aon_compact_rays(dummy, dummy, dummy, dummy, dummy, 4, ip, ip, dummy, dummy, dummy,
+                                  dummy, dummy, nullptr, p, cmp_ws, nullptr),
+                 "compact_rays null n_hit");
+  expect_invalid(aon_compact_rays(dummy, dummy, dummy, dummy, dummy, 4, ip, ip, dummy, dummy, nullptr,
+                                  dummy, dummy, ip, p, cmp_ws, nullptr),
+                 "compact_rays viewdirs without v_out");
+  expect_invalid(aon_compact_rays(dummy, dummy, dummy, dummy, dummy, -1, ip, ip, dummy, dummy, dummy,
+                                  dummy, dummy, ip, p, cmp_ws, nullptr),
+                 "compact_rays B < 0");
+  expect_invalid(aon_compact_rays(dummy, dummy, dummy, dummy, dummy, 4, ip, ip, dummy, dummy, dummy,
+                                  dummy, dummy, ip, p, cmp_ws - 1, nullptr),
+                 "compact_rays work_bytes too small");
+  expect_invalid(aon_scatter_payload(dummy, dummy, dummy, 2, nullptr, 4, 1, dummy, nullptr),
+                 "scatter_payload null slot");
+  expect_invalid(aon_scatter_payload(nullptr, dummy, dummy, 2, ip, 4, 1, dummy, nullptr),
+                 "scatter_payload null comp");
+  expect_invalid(aon_scatter_payload(dummy, dummy, dummy, 2, ip, -1, 1, dummy, nullptr),
+                 "scatter_payload B < 0");
+  if (lim_ws == 0 || cmp_ws == 0 || aon_ray_limits_workspace_bytes(-1) != 0 ||
+      aon_compact_rays_workspace_bytes(-1) != 0 ||
+      aon_ray_limits_workspace_bytes(257) <= aon_ray_limits_workspace_bytes(256) ||
+      aon_compact_rays_workspace_bytes(257) <= aon_compact_rays_workspace_bytes(256)) {
+    std::printf("FAIL box bounds workspace queries\n");
+    ++failures;
+  }
   // size queries: pure host arithmetic
   if (aon_mlp_packed_bytes(AON_PREC_F16X3) == 0 || aon_mlp_bwd_packed_bytes() == 0 ||
       aon_mlp_art_packed_bytes() == 0 || aon_colsum_workspace_bytes(1024, 256) == 0) {

@@ -211,26 +211,74 @@ def sample_pdf(bins, weights, origins, directions, t_vals, num_samples, randomiz
 
 
 # ----------------------------------------------------------------------------- MLP
-def mlp_forward(p, x, condition, netdepth=8, skip_layer=4, netdepth_condition=1):
+def mlp_forward(p, x, condition, netdepth=8, skip_layer=4, netdepth_condition=1, record=None):
     """reference models/vanilla_nerf/model.py:95-120 with ``p`` = {layer.weight/bias: tensor}.
 
     x: (B, S, C) encoded points; condition: (B, Cv) encoded view directions.
-    Returns raw_rgb (B, S, 3), raw_density (B, S, 1).
+    Returns raw_rgb (B, S, 3), raw_density (B, S, 1).  ``record`` (a dict, a test hook) receives
+    the intermediates in :func:`mlp_forward_kept`'s layout.
     """
+    rec = record if record is not None else {}
     S, C = x.shape[1:]
     x = x.reshape(-1, C)
     inputs = x
+    rec.update(enc=x, h=[], hv=[])
     for idx in range(netdepth):
         x = torch.relu(x @ p[f"pts_linears.{idx}.weight"].T + p[f"pts_linears.{idx}.bias"])
+        rec["h"].append(x)
         if idx % skip_layer == 0 and idx > 0:
             x = torch.cat([x, inputs], dim=-1)
     raw_density = (x @ p["density_layer.weight"].T + p["density_layer.bias"]).reshape(-1, S, 1)
-    bottleneck = x @ p["bottleneck_layer.weight"].T + p["bottleneck_layer.bias"]
+    bottleneck = rec["bot"] = x @ p["bottleneck_layer.weight"].T + p["bottleneck_layer.bias"]
     cond = torch.tile(condition[:, None, :], (1, S, 1)).reshape(-1, condition.shape[-1])
     x = torch.cat([bottleneck, cond], dim=-1)
     for idx in range(netdepth_condition):
         x = torch.relu(x @ p[f"views_linear.{idx}.weight"].T + p[f"views_linear.{idx}.bias"])
+        rec["hv"].append(x)
     raw_rgb = (x @ p["rgb_layer.weight"].T + p["rgb_layer.bias"]).reshape(-1, S, 3)
+    return raw_rgb, raw_density
+
+
+def mlp_forward_kept(p, kept, condition, S, skip_layer=4, record=None):
+    """Stage isolation of the vanilla MLP's BACKWARD (model.py:95-120): the forward of
+    :func:`mlp_forward` whose every intermediate VALUE is the one a GPU forward kept -- ``kept``
+    = {enc (R,63) = pos_enc(x), h (8,R,256), bot (R,256), hv (1,R,128)}, ReLU' taken from the
+    sign of the kept activation, every layer's input the kept tensor itself (detached) -- while
+    autograd runs through this function's own linear maps in the parameters' dtype.  Its
+    backward from a given d raw is therefore the exact (e.g. fp64) backward at the GPU's own
+    forward values: each parameter gradient is dZ^T X with X the kept input, and dZ flows down
+    through W and the kept ReLU' pattern only.  condition: (B, 27) encoded view directions.
+    ``record`` (a dict) receives the pre-activation sums -- z (8 x (R,256)), zb (R,256), zv
+    (1 x (R,128)) -- whose ``retain_grad`` gradients are the dL/dZ of each layer.
+    Returns raw_rgb (R, 3), raw_density (R, 1)."""
+    dt = p["rgb_layer.weight"].dtype
+    K = {k: (v.detach().to(dt) if torch.is_tensor(v) else [x.detach().to(dt) for x in v])
+         for k, v in kept.items()}
+    rec = record if record is not None else {}
+    rec.update(z=[], zv=[])
+
+    def forced(value, z):
+        return value + (z - z.detach())
+
+    def relu_kept(value, z):
+        return forced(value, z * (value > 0).to(dt))
+
+    x = inputs = K["enc"]
+    for idx in range(len(K["h"])):
+        z = _lin(p, f"pts_linears.{idx}", x)
+        rec["z"].append(z)
+        x = relu_kept(K["h"][idx], z)
+        if idx % skip_layer == 0 and idx > 0:
+            x = torch.cat([x, inputs], dim=-1)
+    raw_density = _lin(p, "density_layer", x)
+    zb = rec["zb"] = _lin(p, "bottleneck_layer", x)
+    cond = torch.tile(condition.to(dt)[:, None, :], (1, S, 1)).reshape(-1, condition.shape[-1])
+    x = torch.cat([forced(K["bot"], zb), cond], dim=-1)
+    for idx in range(len(K["hv"])):
+        z = _lin(p, f"views_linear.{idx}", x)
+        rec["zv"].append(z)
+        x = relu_kept(K["hv"][idx], z)
+    raw_rgb = _lin(p, "rgb_layer", x)
     return raw_rgb, raw_density
 
 

@@ -761,6 +761,161 @@ def test_backward_gradient_scale_invariance(fused):
             assert torch.equal(a * 2.0 ** -k, b), (k, i, float((a * 2.0 ** -k - b).abs().max()))
 
 
+_LAYER_NAMES = ([f"pts_linears.{i}" for i in range(8)]
+                + ["density_layer", "bottleneck_layer", "views_linear.0", "rgb_layer"])  # _layers()
+_DZ_NAMES = [f"dz{i}" for i in range(8)] + ["dzb", "dzv"]
+
+
+def _nan_padding(x, R):
+    """A tiled kept tensor with the padding rows of its last 16-row tile NaN: never read."""
+    from aonerf import tiles
+
+    rm = tiles.untile(x, x.shape[0])
+    rm[R:] = float("nan")
+    return tiles.tile(rm)
+
+
+def stage_level(B, S, bf16=False):
+    """One fine level's fused training forward on a ragged batch (train._forward_level_fused:
+    the kept activations, tiled, and their ReLU' bits) with everything the stage-isolated
+    backward gates need: the row-major encodings (aon_cast_rays, aon_pos_enc), the tiled copy
+    the fused backward reads in production (aon_cast_rays_tiled, 64 fp32 columns; bf16: the
+    forward's own 128-column bf16 copy), both pre-filled with NaN past row R, the kept tensors
+    row-major (for the fp64 oracle and the all-GEMM backward) and tiled with NaN padding rows
+    (for the fused backward)."""
+    from aonerf import tiles, train
+
+    L = train.L
+    net = _make_trainable(0)
+    gen = torch.Generator().manual_seed(B + S)
+    R, NR = B * S, tiles.rows(B * S)
+    o = (torch.rand(B, 3, generator=gen) - 0.5).cuda()
+    d = torch.nn.functional.normalize(torch.randn(B, 3, generator=gen), dim=-1).cuda()
+    t = (2.0 + 4.0 * torch.rand(B, S, generator=gen)).sort(-1).values.cuda()
+    P = [(m.weight.detach(), m.bias.detach()) for m in net.fine_mlp._layers()]
+    raw = torch.empty((R, 4), device="cuda")
+    masks = torch.empty((9, NR, 8), dtype=torch.int32, device="cuda")
+    if bf16:
+        enc_t = torch.full((NR, 128), float("nan"), device="cuda", dtype=torch.bfloat16)
+    else:
+        enc_t = torch.full((NR, 64), float("nan"), device="cuda")
+        L.call("aon_cast_rays_tiled", L.ptr(o), L.ptr(d), L.ptr(t), B, S, 0, 10, 64, L.ptr(enc_t),
+               L.stream())
+    h_t, bot_t, hv_t = train._forward_level_fused(P, o, d, d, t, raw, None, masks, bf16=bf16,
+                                                  enc=enc_t if bf16 else None)
+    enc = torch.empty((R, 63), device="cuda")
+    L.call("aon_cast_rays", L.ptr(o), L.ptr(d), L.ptr(t), B, S, None, 0, None, 0, 10, L.ptr(enc),
+           L.stream())
+    venc = torch.empty((B, 27), device="cuda")
+    L.call("aon_pos_enc", L.ptr(d), B, 0, 4, L.ptr(venc), L.stream())
+    torch.cuda.synchronize()
+    assert torch.isfinite(raw).all()
+    return dict(P=P, R=R, NR=NR, S=S, gen=gen, rays_d=d, t=t, raw=raw, masks=masks, enc=enc,
+                enc_t=enc_t, venc=venc,
+                h_rm=[tiles.untile(x, R).float() for x in h_t],
+                bot_rm=tiles.untile(bot_t, R).float(), hv_rm=tiles.untile(hv_t, R).float(),
+                h_t=[_nan_padding(x, R) for x in h_t], bot_t=_nan_padding(bot_t, R),
+                hv_t=_nan_padding(hv_t, R))
+
+
+def stage_reference(lv, draw):
+    """The fp64 oracle backward at the GPU forward's own kept values (oracle.mlp_forward_kept)
+    from ``draw`` (R, 4): ({parameter name: gradient}, [dL/dZ of pts_linears.0..7,
+    bottleneck_layer, views_linear.0]) as fp64 numpy arrays."""
+    p64 = {k[len("fine_mlp."):]: torch.from_numpy(v).double().requires_grad_(True)
+           for k, v in W.nerf_state_dict(0).items() if k.startswith("fine_mlp.")}
+    kept = {"enc": lv["enc"].cpu(), "h": [x.cpu() for x in lv["h_rm"]], "bot": lv["bot_rm"].cpu(),
+            "hv": [lv["hv_rm"].cpu()]}
+    pre = {}
+    r_rgb, r_sig = O.mlp_forward_kept(p64, kept, lv["venc"].cpu(), lv["S"], record=pre)
+    zs = pre["z"] + [pre["zb"]] + pre["zv"]
+    for z in zs:
+        z.retain_grad()
+    d64 = draw.cpu().double()
+    torch.autograd.backward([r_rgb, r_sig], [d64[:, :3], d64[:, 3:]])
+    return {k: v.grad.numpy() for k, v in p64.items()}, [z.grad.numpy() for z in zs]
+
+
+def stage_chain(lv, draw, bf16=False):
+    """aon_mlp_bwd[_bf16] alone on the level's ReLU' bits and ``draw``: the untiled dz[0..7],
+    dzb, dzv (outputs pre-filled with NaN: every row below R must be written)."""
+    from aonerf import tiles, train
+
+    L = train.L
+    R, NR = lv["R"], lv["NR"]
+    dt = torch.bfloat16 if bf16 else torch.float32
+    dzv = torch.full((NR, 128), float("nan"), device="cuda", dtype=dt)
+    dzb = torch.full((NR, 256), float("nan"), device="cuda", dtype=dt)
+    dz = torch.full((8, NR, 256), float("nan"), device="cuda", dtype=dt)
+    work = torch.zeros((4,), dtype=torch.int32, device="cuda")
+    packed = train._pack_bwd(lv["P"], draw.device, "stage", bf16)
+    L.call("aon_mlp_bwd_bf16" if bf16 else "aon_mlp_bwd", L.ptr(packed), L.ptr(draw),
+           L.ptr(lv["masks"]), R, L.ptr(dzv), L.ptr(dzb), L.ptr(dz), L.ptr(work), L.stream())
+    L.snapshot_pack(packed)
+    torch.cuda.synchronize()
+    return [tiles.untile(dz[i], R).float() for i in range(8)] + [
+        tiles.untile(dzb, R).float(), tiles.untile(dzv, R).float()]
+
+
+@pytest.mark.parametrize("B,S,scale", [(1, 1, 1e-3), (29, 65, 1e-3), (37, 193, 1e-4),
+                                       (128, 193, 1e-4)],
+                         ids=["one_row", "ragged_13_of_16", "fine193_ragged", "fine193"])
+def test_backward_stage_isolated(B, S, scale):
+    """Stage isolation of the vanilla backward (model.py:95-120), the counterpart of
+    test_gpu_art_train.test_art_backward_stage_isolated: the fused forward's own kept tensors
+    and ReLU' bits and a fixed random d raw go through (a) aon_mlp_bwd + the weight-gradient
+    aon_gemm's on the tiled tensors (train._backward_level_fused, the padding rows of the last
+    tile NaN), (b) the all-GEMM backward on their row-major copies (train._backward_level) and
+    (c) the oracle's fp64 autograd evaluated at exactly those forward values
+    (oracle.mlp_forward_kept).  Every weight and bias gradient of (a) and (b) within 1e-4 of
+    its tensor's max of (c); and aon_mlp_bwd alone: dz[0..7], dzb, dzv against the fp64 dL/dZ
+    of each layer (retain_grad on the pre-activation sums), same gate, every row below R
+    finite.  R = 1885 leaves 13 rows in the last 16-row tile, R = 7141 five, R = 1 one.
+
+    Measured worst tensor (MI355X), fused / GEMM / chain:
+      (1, 1)      8.4e-07 / 4.9e-07 / 8.4e-07
+      (29, 65)    2.4e-06 / 9.6e-07 / 5.7e-07
+      (37, 193)   2.4e-06 / 9.9e-07 / 5.8e-07
+      (128, 193)  9.9e-06 / 9.0e-07 / 6.1e-07   (fused: pts_linears.1.bias, a column sum of dz1)
+    """
+    from aonerf import train
+
+    lv = stage_level(B, S)
+    P, venc = lv["P"], lv["venc"]
+    draw = (torch.randn(lv["R"], 4, generator=lv["gen"]) * scale).cuda()
+    Gf = [(torch.empty_like(w), torch.empty_like(b)) for w, b in P]
+    Gg = [(torch.empty_like(w), torch.empty_like(b)) for w, b in P]
+    train._backward_level_fused(P, Gf, lv["enc_t"], venc, S, lv["h_t"], lv["bot_t"], lv["hv_t"],
+                                draw, lv["masks"], True)
+    train._backward_level(P, Gg, lv["enc"], venc, S, lv["h_rm"], lv["bot_rm"], lv["hv_rm"], draw)
+    dzs = stage_chain(lv, draw)
+    torch.cuda.synchronize()
+    want, want_dz = stage_reference(lv, draw)
+    report, bad = [], []
+    for mode, G in (("fused", Gf), ("gemm", Gg)):
+        worst, worst_name = 0.0, ""
+        for (dw, db), name in zip(G, _LAYER_NAMES):
+            for got, key in ((dw, f"{name}.weight"), (db, f"{name}.bias")):
+                e = rel_err(got.cpu().numpy(), want[key])
+                if not e <= worst:  # (a NaN is the worst)
+                    worst, worst_name = e, key
+                if not e <= 1e-4:
+                    bad.append((mode, key, e))
+        report.append(f"{mode} {worst:.2e} ({worst_name})")
+    worst, worst_name = 0.0, ""
+    for got, w, name in zip(dzs, want_dz, _DZ_NAMES):
+        assert torch.isfinite(got).all(), name
+        e = rel_err(got.cpu().numpy(), w)
+        if e > worst:
+            worst, worst_name = e, name
+        if not e <= 1e-4:
+            bad.append(("chain", name, e))
+    report.append(f"chain {worst:.2e} ({worst_name})")
+    print(f"vanilla backward (B={B}, S={S}) vs fp64 at the GPU's forward values: worst "
+          + ", ".join(report))
+    assert not bad, bad
+
+
 def _step_state(net, opt, train_mod, batch, u_c, u_f, lib=None):
     """One training step + Adam: (loss, grads, params after) as host copies."""
     opt.zero_grad()

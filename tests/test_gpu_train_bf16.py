@@ -13,7 +13,8 @@ import torch
 
 from oracle import nerf_oracle as O
 from oracle import weights as W
-from test_gpu_train import _make_trainable, c5_batch, cuda, rel_err
+from test_gpu_train import (_DZ_NAMES, _LAYER_NAMES, _make_trainable, c5_batch, cuda, rel_err,
+                            stage_chain, stage_level, stage_reference)
 
 pytestmark = pytest.mark.gpu
 
@@ -102,6 +103,65 @@ def test_bf16_train_step_c5(bf16_mode):
             worst_e, worst_c = max(worst_e, e), min(worst_c, cos)
             assert e < 0.03 and cos > 0.999, (pre + n, e, cos)
     print(f"C5 bf16 grads vs fp32 oracle: worst max-rel {worst_e:.2e}, worst cosine {worst_c:.5f}")
+
+
+@pytest.mark.parametrize("B,S", [(29, 65), (128, 193)], ids=["ragged_13_of_16", "fine193"])
+def test_bf16_backward_stage_isolated(B, S):
+    """The vanilla bf16 backward (aon_mlp_bwd_bf16 + the mma_bf16 weight-gradient GEMMs) on its
+    own, the counterpart of test_gpu_art_train_bf16.test_art_bf16_backward_stage_isolated: the
+    fp64 oracle's autograd forced to the bf16 training forward's OWN kept values
+    (oracle.mlp_forward_kept on aon_mlp_fwd_train_bf16's bf16 activations; the encodings fp32 from
+    aon_cast_rays / aon_pos_enc) with OUR d raw (aon_composite_fwd / aon_composite_bwd of an MSE
+    against a random target), the kept tensors' padding rows NaN.  Every parameter's gradient
+    within 3e-2 of its max and cosine >= 0.9999 (the articulated bf16 stage gate), and the
+    chain alone: dz[0..7], dzb, dzv against the fp64 dL/dZ of each layer at the same gate.
+
+    Measured (MI355X), worst max-rel / worst cosine, weight gradients then chain:
+      (29, 65)    6.9e-03 / 0.999982, chain 7.6e-03 / 0.999975
+      (128, 193)  4.9e-03 / 0.999989, chain 9.6e-03 / 0.999976
+    """
+    from aonerf import _lib as L
+    from aonerf import train
+
+    lv = stage_level(B, S, bf16=True)
+    P, raw, t, rays_d = lv["P"], lv["raw"], lv["t"], lv["rays_d"]
+    assert lv["h_t"][0].dtype == torch.bfloat16
+    comp = torch.empty((B, 3), device="cuda")
+    acc = torch.empty((B,), device="cuda")
+    wts = torch.empty((B, S), device="cuda")
+    depth = torch.empty((B,), device="cuda")
+    L.call("aon_composite_fwd", L.ptr(raw), 4, L.ptr(raw[:, 3:]), 4, L.ptr(t), L.ptr(rays_d), B, S,
+           1, L.ACT_VANILLA, L.ptr(comp), L.ptr(acc), L.ptr(wts), L.ptr(depth), L.stream())
+    target = torch.rand((B, 3), generator=lv["gen"]).cuda()
+    g_rgb = (2.0 * (comp - target) / (3 * B)).contiguous()
+    draw = torch.empty((B * S, 4), device="cuda")
+    L.call("aon_composite_bwd", L.ptr(raw), 4, L.ptr(raw[:, 3:]), 4, L.ptr(t), L.ptr(rays_d), B, S,
+           1, L.ACT_VANILLA, L.ptr(g_rgb), None, None, L.ptr(draw), L.ptr(draw[:, 3:]), 4,
+           L.stream())
+    G = [(torch.empty_like(w), torch.empty_like(b)) for w, b in P]
+    train._backward_level_fused(P, G, lv["enc_t"], lv["venc"], S, lv["h_t"], lv["bot_t"],
+                                lv["hv_t"], draw, lv["masks"], True)
+    dzs = stage_chain(lv, draw, bf16=True)
+    torch.cuda.synchronize()
+    want, want_dz = stage_reference(lv, draw)
+    pairs = []
+    for (dw, db), name in zip(G, _LAYER_NAMES):
+        pairs += [(name + ".weight", dw, want[name + ".weight"]), (name + ".bias", db, want[name + ".bias"])]
+    report, bad = [], []
+    for what, items in (("grads", pairs), ("chain", list(zip(_DZ_NAMES, dzs, want_dz)))):
+        worst_e, worst_c = 0.0, 1.0
+        for name, got, w in items:
+            assert torch.isfinite(got).all(), name
+            g_ = got.double().cpu().numpy().reshape(-1)
+            w_ = w.reshape(-1)
+            e = rel_err(g_, w_)
+            cos = float(g_ @ w_ / (np.linalg.norm(g_) * np.linalg.norm(w_) + 1e-300))
+            worst_e, worst_c = max(worst_e, e), min(worst_c, cos)
+            if not (e <= 3e-2 and cos >= 0.9999):
+                bad.append((name, e, cos))
+        report.append(f"{what} max-rel {worst_e:.2e} cosine {worst_c:.6f}")
+    print(f"vanilla bf16 backward stage-isolated (B={B}, S={S}): " + ", ".join(report))
+    assert not bad, bad
 
 
 @pytest.mark.parametrize("mma_bf16,dtype", [(False, torch.float32), (True, torch.float32),

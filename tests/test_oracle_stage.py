@@ -5,7 +5,9 @@
 * ``art_mlp_forward(xp_fixed=own x')`` equals the plain forward and its gradients;
 * ``art_mlp_forward_kept`` fed a forward's OWN intermediates reproduces that forward's raw
   outputs and every parameter / latent gradient (fp64): its backward is the reference
-  model_autodecoder.py:168-239's backward, only evaluated at given forward values.
+  model_autodecoder.py:168-239's backward, only evaluated at given forward values;
+* ``mlp_forward_kept``, its vanilla counterpart (model.py:95-120), likewise -- and the gradients
+  of its recorded pre-activation sums are the dL/dZ the weight gradients are built from.
 """
 import numpy as np
 import torch
@@ -81,3 +83,37 @@ def test_kept_forward_reproduces_backward_fp64():
     for k, v in ref.items():
         s = v.abs().max().item()
         assert (got[k] - v).abs().max().item() <= 1e-12 * max(s, 1e-30), k
+
+
+def test_vanilla_kept_forward_reproduces_backward_fp64():
+    p = {k: v.double().requires_grad_(True)
+         for k, v in O.split_state_dict(W.nerf_state_dict(0))[1].items()}
+    g = torch.Generator().manual_seed(4)
+    B, S = 5, 7
+    pos = ((torch.rand(B, S, 3, generator=g) - 0.5) * 2).double()
+    cond = O.pos_enc(torch.nn.functional.normalize(torch.randn(B, 3, generator=g), dim=-1), 0, 4).double()
+    draw = torch.randn(B * S, 4, generator=g).double()
+    rec = {}
+    rgb, sig = O.mlp_forward(p, O.pos_enc(pos, 0, 10), cond, record=rec)
+    torch.autograd.backward([rgb.reshape(-1, 3), sig.reshape(-1, 1)], [draw[:, :3], draw[:, 3:]])
+    ref = _grads(p, {})
+    kept = {k: ([x.detach() for x in v] if isinstance(v, list) else v.detach()) for k, v in rec.items()}
+    pre = {}
+    r2, s2 = O.mlp_forward_kept(p, kept, cond, S, record=pre)
+    zs = pre["z"] + [pre["zb"]] + pre["zv"]
+    for z in zs:
+        z.retain_grad()
+    np.testing.assert_allclose(r2.detach().numpy(), rgb.reshape(-1, 3).detach().numpy(), rtol=0, atol=1e-12)
+    np.testing.assert_allclose(s2.detach().numpy(), sig.reshape(-1, 1).detach().numpy(), rtol=0, atol=1e-12)
+    torch.autograd.backward([r2, s2], [draw[:, :3], draw[:, 3:]])
+    got = _grads(p, {})
+    assert set(got) == set(ref) and len(ref) == 24
+    for k, v in ref.items():
+        s = v.abs().max().item()
+        assert s > 0 and (got[k] - v).abs().max().item() <= 1e-12 * s, k
+    # the recorded pre-activations' gradients are each layer's dL/dZ: the bias gradient is their
+    # column sum (pts_linears.0..7, bottleneck_layer, views_linear.0 in that order)
+    names = [f"pts_linears.{i}" for i in range(8)] + ["bottleneck_layer", "views_linear.0"]
+    for name, z in zip(names, zs):
+        want = ref[f"{name}.bias"]
+        assert (z.grad.sum(0) - want).abs().max().item() <= 1e-12 * want.abs().max().item(), name

@@ -172,12 +172,6 @@ __device__ __forceinline__ double row_incl_sum(double x) {
   return x;
 }
 
-#ifndef AON_MARCH_DIRECT
-#define AON_MARCH_DIRECT 1  // 0: merged rows staged in LDS and copied out (more LDS per wave)
-#endif
-#ifndef AON_MARCH_PIPE
-#define AON_MARCH_PIPE 0  // 1: the next group's inputs loaded during this group's resampling (resident grid): 7% slower (profiles/r03/ab_march)
-#endif
 #ifndef AON_MARCH_ROWS_OCC
 #define AON_MARCH_ROWS_OCC 5  // waves per SIMD the register budget is built for (92 VGPRs, no spills; 6 and 7 spill and run slower: profiles/r03/ab_march)
 #endif
@@ -186,15 +180,9 @@ struct RayLds {
   float tm[68];      // t (65): the merge's t row
   float cdf[64];     // the CDF; after the inverse CDF: the merge's filled-slot bytes (193)
   float bins[64];    // mids of t (the sort path's samples overwrite cdf + bins: 128 floats)
-#if !AON_MARCH_DIRECT
-  float samp[kNs];
-#endif
 };
 struct WaveLds {
   RayLds r[4];
-#if !AON_MARCH_DIRECT
-  float orow[4 * kNo];  // the four rays' merged rows, contiguous as in t_fine
-#endif
 };
 
 // sorted a[0 .. 64) (a[63] = 1 for a CDF): entries <= x, count_lift<true>(a, 64, x) exactly --
@@ -223,9 +211,7 @@ __global__ __launch_bounds__(64 * kWaves, AON_MARCH_ROWS_OCC) void k_march_rows(
   // a group's per-ray inputs: t and raw of samples q + 16 m and sample 64 ("m = 4", every lane;
   // lane 0's copy is the one used), rays_d.  The last group's rows past B read the last ray (no
   // branches around the loads) and store nothing; 32-bit offsets (the host checks B * (S + Ns)
-  // < 2^31).  AON_MARCH_PIPE: the next group's inputs are loaded while this group resamples
-  // (its t / raw registers are dead by then), so a wave streaming several groups does not wait
-  // on HBM at the top of each.
+  // < 2^31).
   auto load_group = [&](int64_t g, float (&t5)[5], f4 (&r5)[5], float (&d3)[3]) {
     const int64_t ry = 4 * g + row;
     const uint32_t rr = static_cast<uint32_t>(ry < B ? ry : B - 1);
@@ -239,9 +225,6 @@ __global__ __launch_bounds__(64 * kWaves, AON_MARCH_ROWS_OCC) void k_march_rows(
     for (int c = 0; c < 3; ++c) d3[c] = dirs[3 * rr + c];
   };
   int64_t grp = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
-  float ntt[5], nd[3];
-  f4 nrw[5];
-  if (AON_MARCH_PIPE && grp < ngroups) load_group(grp, ntt, nrw, nd);
   for (; grp < ngroups; grp += gstride) {
     const int64_t ray = 4 * grp + row;
     const bool valid = ray < B;
@@ -249,17 +232,7 @@ __global__ __launch_bounds__(64 * kWaves, AON_MARCH_ROWS_OCC) void k_march_rows(
     const uint32_t r0 = rc * kS;
     float tt[5], d3[3];
     f4 rw[5];
-    if (AON_MARCH_PIPE) {
-#pragma unroll
-      for (int m = 0; m < 5; ++m) {
-        tt[m] = ntt[m];
-        rw[m] = nrw[m];
-      }
-#pragma unroll
-      for (int c = 0; c < 3; ++c) d3[c] = nd[c];
-    } else {
-      load_group(grp, tt, rw, d3);
-    }
+    load_group(grp, tt, rw, d3);
     const float dx = d3[0], dy = d3[1], dz = d3[2];
     const float dnorm = sqrtf(fmaf(dz, dz, fmaf(dy, dy, __fmul_rn(dx, dx))));
     // ---- t[i + 1] of sample i = q + 16 m: lane q + 1, or lane 0's block m + 1 (row_ror:15)
@@ -375,7 +348,6 @@ __global__ __launch_bounds__(64 * kWaves, AON_MARCH_ROWS_OCC) void k_march_rows(
       L.bins[16 * m + q] = __fmul_rn(0.5f, __fadd_rn(tn[m], tt[m]));
     }
     if (q == 0) L.tm[64] = tt[4];
-    if (AON_MARCH_PIPE && grp + gstride < ngroups) load_group(grp + gstride, ntt, nrw, nd);
     // wn[m] at lane q = w[q + 16 m + 1] = the pdf's weight w'[q + 16 m]
     float wn[4];
 #pragma unroll
@@ -437,16 +409,6 @@ __global__ __launch_bounds__(64 * kWaves, AON_MARCH_ROWS_OCC) void k_march_rows(
       }
     }
     wave_sync();
-#ifdef AON_MARCH_DEBUG  // debug build: out_w row = [ws, padw, wsum, cdf[0..61]] instead of w
-    if (out_w && valid) {
-      if (q == 0) {
-        out_w[r0] = ws;
-        out_w[r0 + 1] = padw;
-        out_w[r0 + 2] = wsum;
-      }
-      for (int k = q; k < 62; k += 16) out_w[r0 + 3 + k] = L.cdf[k + 1];
-    }
-#endif
     // inverse CDF (helper.py:232-241) for u_j, j = 16 n + q (u loaded here, not with the
     // compositor's inputs: 8 fewer registers live across the compositor; eval mode reads one
     // shared L2-resident row).  The eight searches run level by level (count_le64's probes, all
@@ -503,15 +465,10 @@ __global__ __launch_bounds__(64 * kWaves, AON_MARCH_ROWS_OCC) void k_march_rows(
       if (!(n == 7 && q == 15)) unsorted |= !(smp[n] <= nxt);
     }
     const uint64_t ub = __builtin_amdgcn_ballot_w64(unsorted);
-#if AON_MARCH_DIRECT
     // the merged row goes straight to t_fine: a row's stores land in one ~772-B window, nearly
     // consecutive per instruction (slot j + rank of sample j)
     float* orow = t_out + rc * kNo;
     float* samp = L.cdf;  // cdf + bins, dead after the inverse CDF
-#else
-    float* orow = WL.orow + row * kNo;
-    float* samp = L.samp;
-#endif
     wave_sync();  // the CDF row is read by every search above before it is reused
     if (ub == 0) {
       // merge by the bin hint: sample j's rank in t starts at its lower bin i0 + 1 (t[i0] <=
@@ -557,7 +514,7 @@ __global__ __launch_bounds__(64 * kWaves, AON_MARCH_ROWS_OCC) void k_march_rows(
 #pragma unroll
       for (int n = 0; n < 8; ++n) {
         filled[pos[n]] = 1;
-        if (!AON_MARCH_DIRECT || valid) orow[pos[n]] = smp[n];
+        if (valid) orow[pos[n]] = smp[n];
       }
       wave_sync();
       // the remaining slots take t in order: slot p's rank among the row's empty slots from a
@@ -585,7 +542,7 @@ __global__ __launch_bounds__(64 * kWaves, AON_MARCH_ROWS_OCC) void k_march_rows(
         for (int e = 0; e < 7; ++e) tvv[e] = L.tm[rank[e] < 0 ? 0 : rank[e]];
 #pragma unroll
         for (int e = 0; e < 7; ++e)
-          if (rank[e] >= 0 && (!AON_MARCH_DIRECT || valid)) orow[16 * (i0 + e) + q] = tvv[e];
+          if (rank[e] >= 0 && valid) orow[16 * (i0 + e) + q] = tvv[e];
       }
     } else {
       // some ray of the wave needs the sort: bitonic sort of every row's 128 samples (a sorted
@@ -611,30 +568,18 @@ __global__ __launch_bounds__(64 * kWaves, AON_MARCH_ROWS_OCC) void k_march_rows(
       }
       for (int j = q; j < kNs; j += 16) {
         const float s = samp[j];
-        if (!AON_MARCH_DIRECT || valid) orow[j + count_le(L.tm, kS, s)] = s;
+        if (valid) orow[j + count_le(L.tm, kS, s)] = s;
       }
       for (int i = q; i < kS; i += 16) {
         const float tvv = L.tm[i];
-        if (!AON_MARCH_DIRECT || valid) orow[i + count_lt(samp, kNs, tvv)] = tvv;
+        if (valid) orow[i + count_lt(samp, kNs, tvv)] = tvv;
       }
     }
     wave_sync();
-#if !AON_MARCH_DIRECT
-    // the four merged rows leave as one contiguous run
-    const int64_t nvalid = B - 4 * grp < 4 ? B - 4 * grp : 4;
-    float* og = t_out + 4 * grp * kNo;
-    const int n_out = static_cast<int>(nvalid) * kNo;
-    for (int i = lane; i < n_out; i += 64) og[i] = WL.orow[i];
-    wave_sync();  // LDS reuse by this wave's next group
-#endif
   }
 }
 
 }  // namespace rowm
-
-#ifndef AON_MARCH_ROWS
-#define AON_MARCH_ROWS 1  // 0: the one-ray-per-wave kernel for the render's S = 65 / Ns = 128 too
-#endif
 
 template <int NB, int SC, int NBX>
 static void launch_march(hipStream_t st, const float* raw, const float* t, const float* dirs,
@@ -669,15 +614,12 @@ extern "C" int aon_composite_march(const float* raw, const float* t, const float
 #define AON_MARCH(NB_, SC_, NBX_)                                                                 \
   launch_march<NB_, SC_, NBX_>(st, raw, t, dirs, B, S, white_bkgd, act, u, u_stride, Ns, p2,      \
                                comp_rgb, acc, weights, depth, t_fine)
-  if (AON_MARCH_ROWS && S == rowm::kS && Ns == rowm::kNs && B * rowm::kNo < (int64_t(1) << 31) &&
+  if (S == rowm::kS && Ns == rowm::kNs && B * rowm::kNo < (int64_t(1) << 31) &&
       (u_stride == 0 || B * u_stride < (int64_t(1) << 31))) {
     // the render's coarse level (64 + 1 samples, 128 fine): four rays per wave
     const int64_t groups = (B + 3) / 4;
 #define AON_ROWS(A_)                                                                              \
-  hipLaunchKernelGGL(rowm::k_march_rows<A_>,                                                      \
-                     AON_MARCH_PIPE ? resident_grid(rowm::k_march_rows<A_>, 64 * rowm::kWaves,     \
-                                                    (groups + rowm::kWaves - 1) / rowm::kWaves)    \
-                                    : grid_for(groups, rowm::kWaves, 1 << 16),                     \
+  hipLaunchKernelGGL(rowm::k_march_rows<A_>, grid_for(groups, rowm::kWaves, 1 << 16),             \
                      64 * rowm::kWaves, 0, st, raw, t, dirs, B, white_bkgd, u, u_stride, comp_rgb, \
                      acc, weights, depth, t_fine)
     if (act == AON_ACT_NONE) AON_ROWS(AON_ACT_NONE);

@@ -126,7 +126,7 @@ __global__ __launch_bounds__(GeomH<NCOL>::kThreads, NCOL == 1 ? 2 : 1) void k_ml
     stash[64 * (6 * c + 5)] = __builtin_bit_cast(f4, venc.lo[0][c]);
   }
 
-  FragPipe<WP, AON_PREFETCH, 0, false, 0, BFM || F16W ? kArtMix.hi : (BFV ? kArtMixV.hi : 0), F16W,
+  FragPipe<WP, AON_PREFETCH, false, 0, BFM || F16W ? kArtMix.hi : (BFV ? kArtMixV.hi : 0), F16W,
            X1F>
       fp(p);
   static_assert(kArtMix.lo == 0 && kArtMixV.lo == 0, "mixed streams start fp16x3");

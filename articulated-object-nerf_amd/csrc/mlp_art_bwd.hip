@@ -215,7 +215,7 @@ __global__ __launch_bounds__(ArtBwdGeom<BF>::kThreads, 2) void k_mlp_art_bwd_f16
     stash[64] = __builtin_bit_cast(f4, dsig.lo[0][0]);
   }
 
-  FragPipe<WeightPipeP<Net, G::kThreads, BF>, AON_PREFETCH, 0, BF> fp(p);
+  FragPipe<WeightPipeP<Net, G::kThreads, BF>, AON_PREFETCH, BF> fp(p);
   fp.start();
   lds_float* bias_l = opaque_lds(bias_s + 4 * g);
 

@@ -117,7 +117,7 @@ __global__ __launch_bounds__((GeomH<BF ? kBfNcolBwd : 1, BF>::kThreads), 2) void
     if (!BF) stash[64 * (2 * c + 1)] = __builtin_bit_cast(f4, dsig.lo[0][c]);
   }
 
-  FragPipe<WeightPipeP<Net, G::kThreads, BF>, AON_PREFETCH, 0, BF> fp(p);
+  FragPipe<WeightPipeP<Net, G::kThreads, BF>, AON_PREFETCH, BF> fp(p);
   fp.start();
   lds_float* bias_l = opaque_lds(bias_s + 4 * g);
 

@@ -6,7 +6,7 @@
 // v_mfma_f32_16x16x32_f16 into ONE fp32 accumulator.  That is 3 fp16 MFMAs per 32-deep k-step
 // where the fp32 path needs 8 v_mfma_f32_16x16x4_f32 of twice the cycles: 16/3 = 5.3x the
 // arithmetic rate at fp32-class accuracy (measured against the reference in
-// tests/test_gpu_parity.py).  Scales (exact powers of two, mlp_layout.hpp AON_F16X3_V2):
+// tests/test_gpu_parity.py).  Scales (exact powers of two, mlp_layout.hpp kActS / kWS):
 // activations ride at 2^3 (kActS) and weights at 2^6 (kWS), so the unscaled lo parts stay
 // normal in fp16 for |activation| >= 2^-6 and the products share the accumulator at 2^9; the
 // epilogue folds 2^-6 and the bias into one fma.  fp16 then bounds a hidden activation at
@@ -24,16 +24,6 @@
 namespace aon {
 namespace mlp {
 
-#ifndef AON_STASH_REGS
-#define AON_STASH_REGS 0  // 1: keep the encodings in VGPRs instead of parking them in LDS
-#endif
-
-#ifndef AON_STAGGER
-#define AON_STAGGER 0  // 1: waves 4-7 run their epilogues 4 k-steps later (A/B: no gain, profiles/r02/ab_stagger)
-#endif
-
-// The layer sequence of k_mlp_fwd_f16x3 (model.py:95-120), instantiated per FragPipe type: the
-// two halves of the workgroup differ in the k-step of their epilogues (FragPipe EOFF).
 // per-lane LDS stash of the encodings: enc k-steps 0, 1 and venc, hi and lo (fp16x3) or hi only
 // (bf16: no lo part); slot (c, i) at stash[64 (kStashPer c + i)].  SIG (the density-only pass):
 // no venc slots
@@ -55,19 +45,17 @@ static_assert(kStreamBlocksSigma % kChunkH == 0 &&
                   (kBlocksSigma - 1) / kChunkH == kStreamBlocksSigma / kChunkH - 1,
               "density-only stream: whole ring chunks, none unused");
 
+// The layer sequence of k_mlp_fwd_f16x3 (model.py:95-120)
 template <typename Net, int NCOL, bool STORE, typename T, typename FP>
 __device__ __forceinline__ void vanilla_layers(FP& fp, Frag<2, NCOL>& enc, Frag<1, NCOL>& venc,
                                                Frag<8, NCOL>& x, Frag<8, NCOL>& y, f4* stash,
-                                               float* bias_s, int g, int wave,
+                                               float* bias_s, int g,
                                                const int64_t (&rows)[NCOL], int64_t N, int act,
                                                float* __restrict__ raw, const TrainStore& ts) {
   constexpr bool BF = std::is_same<T, __bf16>::value;
   constexpr bool SIG = kSigmaOnly<Net>;
   static_assert(!SIG || (!STORE && !BF), "the density-only pass is a render pass");
   fp.start();  // begin(0): chunk 0 landed; the barrier also publishes bias_s
-#if AON_PRIO_HALF
-  if (wave >= GeomH<NCOL>::kWaves / 2) __builtin_amdgcn_s_setprio(AON_PRIO_HALF);
-#endif
   lds_float* bias_l = opaque_lds(bias_s + 4 * g);  // this lane group's rows of the bias table
 
   Frag<1, NCOL> none;
@@ -84,7 +72,7 @@ __device__ __forceinline__ void vanilla_layers(FP& fp, Frag<2, NCOL>& enc, Frag<
   layer_h<Net, L3, true>(fp, x, none, y, bias_l, g, SP::make(th + 3 * hs, 256, rows, N, g, ts.masks + 3 * ms));
   layer_h<Net, L4, true>(fp, y, none, x, bias_l, g, SP::make(th + 4 * hs, 256, rows, N, g, ts.masks + 4 * ms));
 #pragma unroll
-  for (int c = 0; c < NCOL && !AON_STASH_REGS; ++c)
+  for (int c = 0; c < NCOL; ++c)
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       enc.hi[k][c] = __builtin_bit_cast(h8, stash[64 * enc_slot<BF, SIG>(c, k, 0)]);
@@ -104,7 +92,7 @@ __device__ __forceinline__ void vanilla_layers(FP& fp, Frag<2, NCOL>& enc, Frag<
     if constexpr (!FOLD)
       layer_h<Net, LBOT, false>(fp, y, none, x, bias_l, g, SP::make(tbot, 256, rows, N, g));
 #pragma unroll
-    for (int c = 0; c < NCOL && !AON_STASH_REGS; ++c) {
+    for (int c = 0; c < NCOL; ++c) {
       venc.hi[0][c] = __builtin_bit_cast(h8, stash[64 * venc_slot<BF>(c, 0)]);
       if (!BF) venc.lo[0][c] = __builtin_bit_cast(h8, stash[64 * venc_slot<BF>(c, 1)]);
     }
@@ -122,14 +110,13 @@ __device__ __forceinline__ void vanilla_layers(FP& fp, Frag<2, NCOL>& enc, Frag<
 #pragma unroll
     for (int c = 0; c < NCOL; ++c) {
       if (rows[c] < N) {
-        const float s = AON_F16X3_V2 ? 1.0f : 1.0f / kActScale;  // V2 heads are at true scale
-        float sig = dens[c][0] * s;
+        float sig = dens[c][0];  // the heads are at true scale
         if (STORE && ts.noise) sig = __fadd_rn(sig, ts.noise[rows[c]]);  // raw_sigma + noise
         f4 o = {0.0f, 0.0f, 0.0f, act_sigma(sig, act)};  // density-only: no colour
         if constexpr (!SIG) {
-          o[0] = act_rgb(rgb[c][0] * s, act);
-          o[1] = act_rgb(rgb[c][1] * s, act);
-          o[2] = act_rgb(rgb[c][2] * s, act);
+          o[0] = act_rgb(rgb[c][0], act);
+          o[1] = act_rgb(rgb[c][1], act);
+          o[2] = act_rgb(rgb[c][2], act);
         }
 #ifdef AON_ABL_NO_RAW_STORE  // timing-only A/B build (fused-pipeline question): no raw store
         if (__builtin_isnan(o[0] + o[1] + o[2] + o[3]))
@@ -159,7 +146,7 @@ __global__ __launch_bounds__((GeomH<NCOL, BF>::kThreads), (GeomH<NCOL, BF>::kWav
   static_assert(!SIG || MODE == 0, "the density-only pass takes MODE 0 inputs");
   // ONE __shared__ object: weight ring | bias table | per-lane stash of the encodings
   constexpr int kPer = stash_per<BF, SIG>() * NCOL;  // f4 per lane: enc 2 k-steps + venc 1, hi (& lo)
-  constexpr int kStash = AON_STASH_REGS ? 0 : G::kWaves * 64 * kPer;
+  constexpr int kStash = G::kWaves * 64 * kPer;
   static_assert((kLdsWeights + Net::kBiasFloats / 4 + kStash) * 16 <= 160 * 1024, "LDS");
   __shared__ f4 smem[kLdsWeights + Net::kBiasFloats / 4 + kStash];
   float* bias_s = reinterpret_cast<float*>(smem + kLdsWeights);
@@ -283,7 +270,7 @@ __global__ __launch_bounds__((GeomH<NCOL, BF>::kThreads), (GeomH<NCOL, BF>::kWav
   // park the encodings in LDS until the skip / view layers need them (frees 24 VGPRs for the
   // fragment prefetch); only the owning lane ever touches its slots
 #pragma unroll
-  for (int c = 0; c < NCOL && !AON_STASH_REGS; ++c) {
+  for (int c = 0; c < NCOL; ++c) {
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       stash[64 * enc_slot<BF, SIG>(c, k, 0)] = __builtin_bit_cast(f4, enc.hi[k][c]);
@@ -298,15 +285,8 @@ __global__ __launch_bounds__((GeomH<NCOL, BF>::kThreads), (GeomH<NCOL, BF>::kWav
   Frag<8, NCOL> x, y;
   using WP = WeightPipeP<Net, G::kThreads, BF>;
   using T = typename std::conditional<BF, __bf16, float>::type;
-  // wave-uniform branch (readfirstlane): the running range masks stay in SGPRs across it
-  // (not the training forward: with its row stores the second copy spills)
-  if (AON_STAGGER && NCOL == 1 && !STORE && __builtin_amdgcn_readfirstlane(wave) >= G::kWaves / 2) {
-    FragPipe<WP, AON_PREFETCH, 4, BF> fp(p);
-    vanilla_layers<Net, NCOL, STORE, T>(fp, enc, venc, x, y, stash, bias_s, g, wave, rows, N, act, raw, ts);
-  } else {
-    FragPipe<WP, AON_PREFETCH, 0, BF> fp(p);
-    vanilla_layers<Net, NCOL, STORE, T>(fp, enc, venc, x, y, stash, bias_s, g, wave, rows, N, act, raw, ts);
-  }
+  FragPipe<WP, AON_PREFETCH, BF> fp(p);
+  vanilla_layers<Net, NCOL, STORE, T>(fp, enc, venc, x, y, stash, bias_s, g, rows, N, act, raw, ts);
   // every split of this launch: the layers' (x, y) and the encodings' (venc.ovf stays 0 in the
   // density-only pass, which splits none); the status word sits behind the WHOLE bias table
   constexpr int kStatusAt = SIG ? NetVanillaFoldH::kBiasFloats : Net::kBiasFloats;
@@ -381,7 +361,6 @@ __global__ void k_pack_h(PackArgsH a, float* __restrict__ out_f) {
           }
         }
       }
-#if AON_F16X3_V2
       if (bf && !a.f16w) {  // bf16 layer: bf16(w), unscaled, in the compact (hi-only) stream
         out[e] = bf_bits(w);
         continue;
@@ -394,24 +373,16 @@ __global__ void k_pack_h(PackArgsH a, float* __restrict__ out_f) {
       // pack_h before this launch; many lanes may store the same value)
       if (!lo_part && !(fabsf(w) <= kF16Max))
         *reinterpret_cast<uint32_t*>(bias_out + a.bias_floats) = 2u;
-#else
-      const _Float16 h = static_cast<_Float16>(w);
-      out[e] = lo_part ? static_cast<_Float16>((w - static_cast<float>(h)) * kLoScale) : h;
-#endif
     } else {
       const int i = static_cast<int>(e - nhalf);
       int li = 0;
       while (li + 1 < a.n_layers && a.layers[li + 1].bias0 <= i) ++li;
       const int o = i - a.layers[li].bias0;
-#if AON_F16X3_V2
       // hidden layers add the bias at activation scale; the 1-tile heads at true scale
       // (bf16 layers: at true scale, their activations are unscaled)
       const StreamMap map{a.bf16, a.mx_lo, a.mx_hi};
       const float bs =
           a.layers[li].u == 1 || !(map.f16(a.layers[li].blk0) || a.f16w) ? 1.0f : kActS;
-#else
-      const float bs = kActScale;
-#endif
       float b = (o < a.layers[li].out_real && a.b[li]) ? a.b[li][o] : 0.f;
       if (a.fold_w && li == a.fold_layer && o < a.layers[li].out_real) {
         // folded bias: b[o] + sum_j w[o][j] fold_b[j], fp64 in index order, rounded once

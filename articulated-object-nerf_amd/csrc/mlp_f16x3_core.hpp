@@ -15,10 +15,6 @@ namespace mlp {
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 
-#ifndef AON_FMA_MIX
-#define AON_FMA_MIX 1
-#endif
-
 __device__ __forceinline__ f4 mfma16(h8 a, h8 b, f4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
 }
@@ -38,16 +34,12 @@ __device__ __forceinline__ _Float16 bf_bits(float v) {
   return __builtin_bit_cast(_Float16, static_cast<__bf16>(v));  // round to nearest even
 }
 
-// fp32 value (already at activation scale) -> (hi, lo) fp16 pair: V2 lo = x - hi (exact in
-// fp32, normal in fp16 for |x| >= 2^-3 at scale); V1 lo = (x - hi) * 2^11
+// fp32 value (already at activation scale) -> (hi, lo) fp16 pair: lo = x - hi (exact in fp32,
+// normal in fp16 for |x| >= 2^-3 at scale)
 __device__ __forceinline__ _Float16 lo_of(float v, _Float16 h) {
-#if AON_F16X3_V2
   // v - hi is exact in fp32; as an fma with the fp16 operand widened in the instruction it can
   // issue as one v_fma_mix_f32 instead of v_cvt_f32_f16 + v_sub_f32
   return static_cast<_Float16>(__builtin_fmaf(static_cast<float>(h), -1.0f, v));
-#else
-  return static_cast<_Float16>(__fmul_rn(__fsub_rn(v, static_cast<float>(h)), kLoScale));
-#endif
 }
 
 // Range guard.  fp16 holds |x| <= 65504: at the 2^3 activation scale a hidden activation past
@@ -63,9 +55,7 @@ constexpr float kF16Max = 65504.0f;
 // ovf |= ballot(bad): the running OR is pinned to one SGPR pair per step (an empty asm on it);
 // left to itself hipcc keeps every ballot live until the final OR, and the hundreds of mask
 // pairs spill into VGPR lanes (1,072 v_writelane / v_readlane in the vanilla kernel, -5%)
-#ifndef AON_PIN_OVF
 #define AON_PIN_OVF(v) asm("" : "+s"(v))
-#endif
 #ifndef AON_RANGE_GUARD
 #define AON_RANGE_GUARD 1  // 0: timing-only A/B build without the range test
 #endif
@@ -82,10 +72,10 @@ __device__ __forceinline__ void range_report(const float* bias_end, uint64_t ovf
   if (ovf && (threadIdx.x & 63) == 0) *reinterpret_cast<uint32_t*>(const_cast<float*>(bias_end)) = 1u;
 }
 
-// operand scale of a layer's input activations: 2^3 for fp16x3 (V2), 1 for bf16 layers (bf16
+// operand scale of a layer's input activations: 2^3 for fp16x3, 1 for bf16 layers (bf16
 // has fp32's exponent range: no scaling, and their weights are packed unscaled too)
 template <bool BF>
-__host__ __device__ constexpr float act_scale() { return BF ? 1.0f : (AON_F16X3_V2 ? kActS : kActScale); }
+__host__ __device__ constexpr float act_scale() { return BF ? 1.0f : kActS; }
 
 // 8 fp32 values (already at activation scale) -> (hi, lo) fp16 fragments; ovf |= out of range.
 // BF: bf16 values in hi, no lo, no range test.
@@ -111,18 +101,10 @@ __device__ __forceinline__ void split8(const float (&v)[8], h8& hi, h8& lo, uint
 // stream order (2 per (u, k-step)), so the step after block b is always b + 2.  The hi/lo pair
 // of the NEXT step is read from LDS before the MFMAs of the current step are issued, hiding the
 // LDS latency behind 3*NCOL MFMAs (hipcc issues ds_read -> lgkmcnt(0) -> MFMA otherwise).
-#ifndef AON_SCHED_MASK
-#define AON_SCHED_MASK 0
-#endif
-
 #ifndef AON_PREFETCH
 #define AON_PREFETCH 3
 #endif
 
-// EOFF: the k-step at which a layer starts the pending pair's epilogue (layer_h).  Waves
-// w and w + 4 of an 8-wave workgroup share a SIMD; run in lockstep they reach the epilogue VALU
-// and the epilogue-free MFMA steps together, so neither wave's VALU rides beside the other's
-// MFMAs.  Waves 4-7 take EOFF = 4 (a stagger: MI355X_MICROARCH.md "Two waves per SIMD" item 9).
 // BF: bf16 numerics -- the compact stream (WeightPipeP) of hi blocks only.  MXL < MXH: the
 // mixed stream (StreamMap mode 2): layers in the fp16x3 blocks [MXL, MXH) run fp16x3, the
 // others bf16 (layer_h / head_h ask f16_block(d.blk0)).
@@ -133,10 +115,9 @@ __device__ __forceinline__ void split8(const float (&v)[8], h8& hi, h8& lo, uint
 // X1F >= 0: the layers from fp16x3 block X1F on run two fp16 MFMAs per product the other way
 // round, (hi(W) + lo(W)) x hi(x) -- the weights keep their exact split, the activations round
 // once to fp16 (per sample, 2^-11 relative; their lo parts are never formed).
-template <typename P, int D = AON_PREFETCH, int EOFF = 0, bool BF = false, int MXL = 0, int MXH = 0,
+template <typename P, int D = AON_PREFETCH, bool BF = false, int MXL = 0, int MXH = 0,
           bool W1 = false, int X1F = -1>
 struct FragPipe {
-  static constexpr int kEpiOff = EOFF;
   static constexpr bool kW1 = W1;
   static constexpr int kX1From = X1F;
   static constexpr int kMode = MXH > MXL ? 2 : (BF ? 1 : 0);
@@ -173,7 +154,7 @@ struct FragPipe {
     }
     fetch_into(blk + 2 * D, nh[D - 1], nl[D - 1]);
     // keep the prefetch reads above this step's MFMAs (hipcc otherwise sinks them to their use)
-    __builtin_amdgcn_sched_barrier(AON_SCHED_MASK);
+    __builtin_amdgcn_sched_barrier(0);
   }
 };
 
@@ -262,28 +243,12 @@ __device__ __forceinline__ uint32_t cvt_pk_bf16(float lo, float hi) {
   return r;
 }
 
-// Stores of the kept tensors (activations, ReLU' bits, the chains' gradients): read once, by a
-// later kernel, long after -- AON_NT_STORE = 1 (A/B build) marks them non-temporal
-#ifndef AON_NT_STORE
-#define AON_NT_STORE 0
-#endif
+// Stores of the kept tensors (activations, ReLU' bits, the chains' gradients)
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 template <typename V>
 __device__ __forceinline__ void kept_store(void* p, V v) {
-#if AON_NT_STORE
-  __builtin_nontemporal_store(v, static_cast<V*>(p));
-#else
   *static_cast<V*>(p) = v;
-#endif
-}
-
-// two consecutive outputs at true scale: one 8-B fp32 store, or (bf16 mode) one 4-B bf16 store
-__device__ __forceinline__ void store2(float* p, float v0, float v1) {
-  kept_store(p, u32x2{__float_as_uint(v0), __float_as_uint(v1)});
-}
-__device__ __forceinline__ void store2(__bf16* p, float v0, float v1) {
-  kept_store(p, __builtin_bit_cast(uint32_t, bf2{static_cast<__bf16>(v0), static_cast<__bf16>(v1)}));
 }
 
 // four consecutive outputs: one 16-B fp32 store, or one 8-B bf16 store
@@ -296,9 +261,6 @@ __device__ __forceinline__ void store4(__bf16* p, float v0, float v1, float v2, 
   kept_store(p, u32x2{__builtin_bit_cast(uint32_t, a), __builtin_bit_cast(uint32_t, b)});
 }
 
-#ifndef AON_TILED
-#define AON_TILED 1  // 0: row-major (A/B only: the training forward's stores 15-45% slower)
-#endif
 // Layout of the tensors the fused training kernels keep for the backward (activations, the
 // chains' pre-activation gradients, ReLU' bits): 16 x 16 tiles, each contiguous and row-major,
 // element (row, f) of a width-ld tensor at (row / 16) 16 ld + 256 (f / 16) + 16 (row % 16) +
@@ -307,33 +269,29 @@ __device__ __forceinline__ void store4(__bf16* p, float v0, float v1, float v2, 
 // pieces (row-major stores held the bf16 training forward at 2.9 ms; tiled 1.5 ms,
 // profiles/r02/ab_tiled), and the weight-gradient GEMM still reads 64-B row runs.  Buffers
 // hold act_rows(N) = N rounded up to 16 rows.
-__host__ __device__ constexpr int64_t act_rows(int64_t N) { return AON_TILED ? (N + 15) & ~int64_t(15) : N; }
+__host__ __device__ constexpr int64_t act_rows(int64_t N) { return (N + 15) & ~int64_t(15); }
 __device__ __forceinline__ int64_t act_base(int64_t row, int ld, int g) {
-  return AON_TILED ? (row & ~int64_t(15)) * ld + 16 * (row & 15) + 4 * g : row * ld + 4 * g;
+  return (row & ~int64_t(15)) * ld + 16 * (row & 15) + 4 * g;
 }
-// uint2 index of the ReLU' word (row, g): [N][4], or tiled [N/16][64 lanes]
+// uint2 index of the ReLU' word (row, g): tiled [N/16][64 lanes]
 __device__ __forceinline__ int64_t mask_index(int64_t row, int g) {
-  return AON_TILED ? (row & ~int64_t(15)) * 4 + 16 * g + (row & 15) : row * 4 + g;
+  return (row & ~int64_t(15)) * 4 + 16 * g + (row & 15);
 }
-constexpr int kTileStride = AON_TILED ? 256 : 16;  // elements between output tiles of one lane
-// Whether a sample's kept values are stored.  Tiled: the whole 16-row tile is stored when it
+constexpr int kTileStride = 256;  // elements between output tiles of one lane
+// Whether a sample's kept values are stored: the whole 16-row tile is stored when it
 // starts below N -- the kept tensors hold act_rows(N) rows, so its rows past N land in the
 // padding (never read: the weight-gradient kernels stop at row N) -- and the test is
 // wave-uniform (readfirstlane of the tile's first row), so every store of the epilogues branches
 // on SCC instead of masking EXEC around itself (s_and_saveexec / s_cbranch_execz / s_or per
-// store).  Row-major (A/B build): row < N.
+// store).
 __device__ __forceinline__ bool keep_row(int64_t row, int64_t N) {
 #ifdef AON_ABL_NO_KEEP  // timing-only A/B build: the training kernels store nothing they keep
   return false;
 #endif
-#if AON_TILED
   const uint64_t t = static_cast<uint64_t>(row & ~int64_t(15));
   const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(t));
   const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(t >> 32));
   return static_cast<int64_t>((static_cast<uint64_t>(hi) << 32) | lo) < N;
-#else
-  return row < N;
-#endif
 }
 
 // bf16 training modes: pos_enc(x) kept for the weight gradients of pts_linears.0 and the skip
@@ -377,12 +335,6 @@ __device__ __forceinline__ void store_enc_f32(float* base, int64_t row, int g,
 // x' (columns 0..2) of a store_enc_f32<EW> tensor
 __device__ __forceinline__ int64_t enc_x_index(int64_t row, int EW) { return act_base(row, EW, 0); }
 
-#ifndef AON_BF_ST16
-#define AON_BF_ST16 1
-#endif
-#ifndef AON_PK_F16X3_BF
-#define AON_PK_F16X3_BF 1  // 0: A/B build -- fp32 ReLU' compares and per-value scaling (RowStore::put)
-#endif
 template <typename S, typename = void>
 struct pk_from_f32 : std::false_type {};
 template <typename S>
@@ -392,22 +344,15 @@ struct pk_from_f32<S, std::void_t<decltype(S::kPkFromF32)>> : std::bool_constant
 // a tile row meet in ONE 16-B store per lane (the wave writes a whole 1-KB tile) instead of two
 // 8-B stores -- the kept stores are issue-bound (profiles/r05/vmcnt_ab/), and the 16-B form cut
 // the C5 f16x3 step 14.06 -> 13.38 ms (forward -7%, chain -9%; articulated forward -10%,
-// profiles/r05/st16_ab/).  0: the 8-B form (A/B).
-#ifndef AON_F32_ST16
-#define AON_F32_ST16 1
-#endif
+// profiles/r05/st16_ab/).
 template <int NCOL, typename T>
 struct Store4 {
   bool ok[NCOL];  // keep_row of each column's sample (wave-uniform when tiled)
   mutable float pend[NCOL][2];
   __device__ __forceinline__ void emit(T* rowp, int pr, int uu, int r0, int c, float v0,
                                        float v1) const {
-    // fp32: one 16-B store per tile row (AON_F32_ST16; 0: one 8-B store per part); bf16: the
-    // two parts of a tile row meet in one 8-B store (4-B stores: 1.73 -> 1.51 ms forward)
-    if (std::is_same<T, float>::value && !AON_F32_ST16) {
-      if (ok[c]) store2(rowp + kTileStride * (2 * pr + uu) + r0, v0, v1);
-      return;
-    }
+    // fp32: one 16-B store per tile row; bf16: the two parts of a tile row meet in one 8-B
+    // store (4-B stores: 1.73 -> 1.51 ms forward)
     if (r0 == 0) {
       pend[c][0] = v0;
       pend[c][1] = v1;
@@ -415,7 +360,7 @@ struct Store4 {
       store4(rowp + kTileStride * (2 * pr + uu), pend[c][0], pend[c][1], v0, v1);
     }
   }
-  // bf16 layers: the packed pair as it is.  AON_BF_ST16 (tiled): the pair's two tiles meet in
+  // bf16 layers: the packed pair as it is.  The pair's two tiles meet in
   // ONE 16-B store per lane -- lane (g, j) holds 4 features of tile 2pr and 4 of tile 2pr + 1
   // (4g.., 16 + 4g.. of sample j); one v_permlane16_swap per dword trades the odd lane groups'
   // tile-2pr values for the even groups' tile-(2pr + 1) values, after which group g holds 8
@@ -423,7 +368,6 @@ struct Store4 {
   // 2pr + 1) -- a wave's store is the pair's whole 1-KB run, half the store instructions of the
   // 8-B form (the bf16 chain was store-issue-bound: ~6 B/cycle/CU with 8-B stores).  off16:
   // this lane group's element offset of that run from rowp (set by the makers; 0 or 252).
-  // Else: parts r0 = 0, 2 of a tile row -> one 8-B store.
   static constexpr bool kPkEpi = true;
   __device__ __forceinline__ uint32_t post_pk(int, int, int, int, uint32_t pk) const { return pk; }
   mutable uint32_t pendw[NCOL];
@@ -435,7 +379,6 @@ struct Store4 {
       pendw[c] = pk;
       return;
     }
-#if AON_BF_ST16 && AON_TILED
     if (uu == 0) {
       pend0[c] = uint2{pendw[c], pk};
       return;
@@ -444,9 +387,6 @@ struct Store4 {
     const auto s0 = __builtin_amdgcn_permlane16_swap(pend0[c].x, pendw[c], false, false);
     const auto s1 = __builtin_amdgcn_permlane16_swap(pend0[c].y, pk, false, false);
     if (ok[c]) kept_store(rowp + kTileStride * 2 * pr + off16, u32x4{s0[0], s1[0], s0[1], s1[1]});
-#else
-    if (ok[c]) kept_store(rowp + kTileStride * (2 * pr + uu), u32x2{pendw[c], pk});
-#endif
   }
 };
 // Store4::off16 of lane group g: 16-B run of 8 features of tile 2pr + (g & 1) at column 8 (g / 2),
@@ -457,7 +397,7 @@ template <int NCOL, typename T = float>
 struct RowStore : Store4<NCOL, T> {
   // fp16x3 layers keeping bf16 (the articulated bf16 mode's forward): a ReLU layer's pair is
   // converted once at activation scale and stored / bit-tested packed (epi_part, put_pk)
-  static constexpr bool kPkFromF32 = std::is_same<T, __bf16>::value && AON_F16X3_V2 && AON_PK_F16X3_BF;
+  static constexpr bool kPkFromF32 = std::is_same<T, __bf16>::value;
   T* rowp[NCOL];  // act_base(row) of each column's sample (stored when ok)
   float s;        // to true scale (a power of two: exact)
   __device__ __forceinline__ void begin_pair(int) const {}
@@ -479,19 +419,16 @@ struct RowStore : Store4<NCOL, T> {
 // ONCE (8 B) at its last pair, instead of a byte store per pair (+ a zero byte per pair of a
 // 128-wide layer): bf16 forward 1.239 -> 1.219 ms, articulated 2.706 -> 2.666 ms
 // (profiles/r05/maskword_ab/).  fp32 forwards keep the byte stores (the gathered word spills
-// them: 182-207 VGPRs).  0: byte stores everywhere (A/B).
-#ifndef AON_MASK_WORD
-#define AON_MASK_WORD 1
-#endif
+// them: 182-207 VGPRs).
 template <int NCOL, typename T = float>
 struct RowStoreBits : RowStore<NCOL, T> {
   uint8_t* mrow[NCOL];  // bytes of word (row, g) (stored when ok)
   bool narrow;          // 4-pair (128-wide) layer: bytes 4..7 of the word are written as 0
   mutable uint32_t b[NCOL];  // the current pair's 8 bits (byte pr of the word)
-  mutable uint32_t wlo[NCOL], whi[NCOL];  // AON_MASK_WORD: bytes 0..3 / 4..7 gathered so far
+  mutable uint32_t wlo[NCOL], whi[NCOL];  // bf16: bytes 0..3 / 4..7 gathered so far
   // the finished byte of pair pr: kept and, at the layer's last pair, the whole word stored
   __device__ __forceinline__ void byte_done(int pr, int c, uint32_t byte) const {
-    if constexpr (AON_MASK_WORD && std::is_same<T, __bf16>::value) {  // (fp32 forwards: spills)
+    if constexpr (std::is_same<T, __bf16>::value) {  // (fp32 forwards: spills)
     if (pr < 4) wlo[c] = pr == 0 ? byte : (wlo[c] | (byte << (8 * pr)));
     else whi[c] = pr == 4 ? byte : (whi[c] | (byte << (8 * (pr - 4))));
     if (this->ok[c]) {
@@ -613,7 +550,7 @@ struct StorePick<true, NCOL, T> {
       r.rowp[c] = base + act_base(rows[c], ld, g);
     }
     r.off16 = st16_off(g);
-    r.s = AON_F16X3_V2 ? 1.0f / kActS : 1.0f / kActScale;
+    r.s = 1.0f / kActS;
     return r;
   }
   // a ReLU layer: also its ReLU' bits at mbase ([N][4] uint2); ld / 32 output pairs
@@ -644,6 +581,7 @@ struct StorePick<true, NCOL, T> {
 // OBF: a fp16x3 layer whose consumer is a bf16 layer (the view-branch mixed stream's bottleneck):
 // its output fragment is bf16 at true scale -- one v_cvt_pk_bf16_f32 of v * 2^-3 (exact), the
 // same values the kept (bf16) store gets -- instead of the fp16 hi / lo split.
+// xx: unused (layer_h).
 template <bool RELU, bool BF, int NCOL, int NO, typename Store = NoStore, bool ZB = false,
           bool OBF = false>
 __device__ __forceinline__ void epi_part(int q, const f4 (&hh)[2][NCOL], const f4 (&xx)[2][NCOL],
@@ -666,14 +604,9 @@ __device__ __forceinline__ void epi_part(int q, const f4 (&hh)[2][NCOL], const f
     float vv[2];
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
-#if AON_F16X3_V2
       // fp16x3: one accumulator at scale 2^9 -> activation scale 2^3, plus the (pre-scaled) bias
       float v = BF ? hh[uu][c][r0 + e] : fmaf(hh[uu][c][r0 + e], 1.0f / kWS, bias[uu][r0 + e]);
       (void)xx;
-#else
-      float v = fmaf(xx[uu][c][r0 + e], 1.0f / kLoScale, hh[uu][c][r0 + e]);
-      (void)bias;
-#endif
       if (RELU) v = fmaxf(v, 0.0f);
       vv[e] = st.post(pr, uu, r0 + e, c, v);
     }
@@ -690,7 +623,7 @@ __device__ __forceinline__ void epi_part(int q, const f4 (&hh)[2][NCOL], const f
       continue;
     }
     if constexpr (OBF) {
-      static_assert(AON_F16X3_V2 && !RELU, "OBF: a V2 layer without ReLU (the bottleneck)");
+      static_assert(!RELU, "OBF: a layer without ReLU (the bottleneck)");
       st.put(pr, uu, r0, c, vv[0], vv[1]);
       const uint32_t pk = cvt_pk_bf16(vv[0] * (1.0f / kActS), vv[1] * (1.0f / kActS));
       u4 w = __builtin_bit_cast(u4, out.hi[pr][c]);
@@ -698,7 +631,7 @@ __device__ __forceinline__ void epi_part(int q, const f4 (&hh)[2][NCOL], const f
       out.hi[pr][c] = __builtin_bit_cast(h8, w);
       continue;
     }
-#if !(AON_GUARD_PK && AON_F16X3_V2 && AON_FMA_MIX)
+#if !AON_GUARD_PK
     or_ballot(out.ovf, fmaxf(fabsf(vv[0]), fabsf(vv[1])) > kF16Max);
 #endif
     if constexpr (RELU && pk_from_f32<Store>::value) {
@@ -710,7 +643,6 @@ __device__ __forceinline__ void epi_part(int q, const f4 (&hh)[2][NCOL], const f
     } else {
       st.put(pr, uu, r0, c, vv[0], vv[1]);
     }
-#if AON_F16X3_V2 && AON_FMA_MIX
     // hi pair by one v_cvt_pk_f16_f32; lo_e = v_e - hi_e by v_fma_mix_f32 reading the fp16 half
     // in place (exact in fp32), then one more cvt_pk
     typedef _Float16 h2 __attribute__((ext_vector_type(2)));
@@ -729,14 +661,6 @@ __device__ __forceinline__ void epi_part(int q, const f4 (&hh)[2][NCOL], const f
     out.hi[pr][c][2 * q + 1] = hp[1];
     out.lo[pr][c][2 * q] = static_cast<_Float16>(d0);
     out.lo[pr][c][2 * q + 1] = static_cast<_Float16>(d1);
-#else
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const _Float16 h = static_cast<_Float16>(vv[e]);
-      out.hi[pr][c][2 * q + e] = h;
-      out.lo[pr][c][2 * q + e] = lo_of(vv[e], h);
-    }
-#endif
   }
 }
 
@@ -750,15 +674,18 @@ __device__ __forceinline__ void layer_h(P& p, const Frag<NA, NCOL>& a,
   constexpr LayerDesc d = Net::layer(LAYER);
   constexpr int K = d.ka + d.kb;
   constexpr int NP = d.u / 2;
-  constexpr int EO = P::kEpiOff;  // epilogue parts of pair p-1 at k-steps EO..EO+3 of pair p
   constexpr bool CMP = !P::f16_block(d.blk0);  // a compact (hi-only) block of the stream
   constexpr bool BF = CMP && !P::kW1;  // bf16 numerics: one MFMA per k-step and tile
   constexpr bool W1 = CMP && P::kW1;   // fp16 weights: two MFMAs, the fp16x3 epilogue
   constexpr bool X1 = !CMP && P::kX1From >= 0 && d.blk0 >= P::kX1From;  // fp16 activations
-  constexpr int QIN = K - EO < 0 ? 0 : (K - EO > 4 ? 4 : K - EO);  // parts done inside the loop
+  constexpr int QIN = K < 4 ? K : 4;  // epilogue parts of pair p-1 done at k-steps 0..3 of pair p
   static_assert(d.u % 2 == 0 && NP <= NO && d.ka <= NA && d.kb <= NB, "layer shape");
+  // xx / pxx: the second accumulator set of the retired two-accumulator scale scheme.  Nothing
+  // accumulates into it (it stays zero and compiles away), but taking the dead arrays out of
+  // layer_h and epi_part reorders a few s_nop / ds_read pairs in the kernels' schedules, so
+  // they stay until a change that is benchmarked removes them.
   f4 phh[2][NCOL], pxx[2][NCOL];  // accumulators of the pair whose epilogue is pending
-  f4 pbias[2];                     // V2: that pair's biases, added in its epilogue
+  f4 pbias[2];                     // that pair's biases, added in its epilogue
   // bf16 layers seed the accumulators with the bias (no epilogue add); each pair's bias is read
   // from LDS one pair ahead, so the first MFMA does not wait on it (zero-bias chains: nothing)
   constexpr bool kBiasC = BF && !Net::kZeroBias;
@@ -781,12 +708,8 @@ __device__ __forceinline__ void layer_h(P& p, const Frag<NA, NCOL>& a,
         bias[uu] = f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int c = 0; c < NCOL; ++c) {
-#if AON_F16X3_V2
         // fp16x3: the bias joins in the epilogue (no LDS read to wait on); bf16: in the accumulator
         hh[uu][c] = kBiasC ? bias[uu] : f4{0.f, 0.f, 0.f, 0.f};
-#else
-        hh[uu][c] = bias[uu];
-#endif
         xx[uu][c] = f4{0.f, 0.f, 0.f, 0.f};
       }
     }
@@ -807,7 +730,6 @@ __device__ __forceinline__ void layer_h(P& p, const Frag<NA, NCOL>& a,
           const int ia = k < NA ? k : 0, ib = (k >= d.ka && k - d.ka < NB) ? k - d.ka : 0;
           const h8 xh = k < d.ka ? a.hi[ia][c] : b.hi[ib][c];
           const h8 xl = k < d.ka ? a.lo[ia][c] : b.lo[ib][c];
-#if AON_F16X3_V2
           if (BF) {
             hh[uu][c] = mfma_bf(wh, xh, hh[uu][c]);
             (void)xl;
@@ -826,15 +748,10 @@ __device__ __forceinline__ void layer_h(P& p, const Frag<NA, NCOL>& a,
             continue;
           }
           hh[uu][c] = mfma16(wl, xh, hh[uu][c]);
-#else
-          hh[uu][c] = mfma16(wh, xh, hh[uu][c]);
-          xx[uu][c] = mfma16(wh, xl, xx[uu][c]);
-          xx[uu][c] = mfma16(wl, xh, xx[uu][c]);
-#endif
         }
       }
-      if (pr > 0 && k >= EO && k - EO < 4)
-        epi_part<RELU, BF, NCOL, NO, Store, Net::kZeroBias, OBF>(k - EO, phh, pxx, pbias, out, pr - 1, st);
+      if (pr > 0 && k < 4)
+        epi_part<RELU, BF, NCOL, NO, Store, Net::kZeroBias, OBF>(k, phh, pxx, pbias, out, pr - 1, st);
     }
     if (pr > 0) {
 #pragma unroll
@@ -865,17 +782,10 @@ __device__ __forceinline__ void head_h(P& p, const Frag<NA, NCOL>& a, f4 (&res)[
   constexpr bool BF = CMP && !P::kW1, W1 = CMP && P::kW1;
   constexpr bool X1 = !CMP && P::kX1From >= 0 && d.blk0 >= P::kX1From;
   static_assert(d.u == 1 && d.kb == 0 && d.ka <= NA, "head shape");
-  f4 hh[NCOL], xx[NCOL];
+  f4 hh[NCOL];
   const f4 bias = *reinterpret_cast<lds_f4*>(bias_l + d.bias0);
 #pragma unroll
-  for (int c = 0; c < NCOL; ++c) {
-#if AON_F16X3_V2
-    hh[c] = f4{0.f, 0.f, 0.f, 0.f};
-#else
-    hh[c] = bias;
-#endif
-    xx[c] = f4{0.f, 0.f, 0.f, 0.f};
-  }
+  for (int c = 0; c < NCOL; ++c) hh[c] = f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int k = 0; k < d.ka; ++k) {
     const int blk = d.blk0 + 2 * k;
@@ -883,7 +793,6 @@ __device__ __forceinline__ void head_h(P& p, const Frag<NA, NCOL>& a, f4 (&res)[
     p.take(blk, wh, wl);
 #pragma unroll
     for (int c = 0; c < NCOL; ++c) {
-#if AON_F16X3_V2
       if (BF) {
         hh[c] = mfma_bf(wh, a.hi[k][c], hh[c]);
         continue;
@@ -891,23 +800,14 @@ __device__ __forceinline__ void head_h(P& p, const Frag<NA, NCOL>& a, f4 (&res)[
       hh[c] = mfma16(wh, a.hi[k][c], hh[c]);
       if (!X1) hh[c] = mfma16(wh, a.lo[k][c], hh[c]);
       if (!W1) hh[c] = mfma16(wl, a.hi[k][c], hh[c]);
-#else
-      hh[c] = mfma16(wh, a.hi[k][c], hh[c]);
-      xx[c] = mfma16(wh, a.lo[k][c], xx[c]);
-      xx[c] = mfma16(wl, a.hi[k][c], xx[c]);
-#endif
     }
   }
 #pragma unroll
   for (int c = 0; c < NCOL; ++c)
 #pragma unroll
     for (int r = 0; r < 4; ++r)
-#if AON_F16X3_V2
       // true scale (head bias unscaled); bf16 heads: unscaled operands
       res[c][r] = BF ? __fadd_rn(hh[c][r], bias[r]) : fmaf(hh[c][r], 1.0f / (kWS * kActS), bias[r]);
-#else
-      res[c][r] = fmaf(xx[c][r], 1.0f / kLoScale, hh[c][r]);
-#endif
 }
 
 #ifndef AON_RING

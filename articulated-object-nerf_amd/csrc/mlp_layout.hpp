@@ -89,17 +89,10 @@ constexpr int kBlocksFold = 2088;                                  // kBlocks - 
 constexpr int kStreamBlocksFold = (kBlocksFold + 63) / 64 * 64;   // 2112
 constexpr int kBiasFloatsFold = 2208;                              // kBiasFloats - 256
 
-// V1 numerics (AON_F16X3_V2 = 0, kept for A/B only): activations and biases carried at 2^-8,
-// lo halves at 2^11, two accumulators
-constexpr float kActScale = 1.0f / 256.0f;
-constexpr float kLoScale = 2048.0f;
-// V2 numerics (AON_F16X3_V2, the default): activations carried at 2^3, weights at 2^6, so the
-// lo parts (x - fp16(x)) stay in fp16's normal range unscaled and hi*hi, hi*lo, lo*hi share ONE
-// fp32 accumulator at scale 2^9; the epilogue folds the 2^-6 and the bias into one fma.  A
-// hidden activation past 65504 / 2^3 overflows the hi part: the range guard reports it.
-#ifndef AON_F16X3_V2
-#define AON_F16X3_V2 1
-#endif
+// fp16x3 numerics: activations carried at 2^3, weights at 2^6, so the lo parts (x - fp16(x))
+// stay in fp16's normal range unscaled and hi*hi, hi*lo, lo*hi share ONE fp32 accumulator at
+// scale 2^9; the epilogue folds the 2^-6 and the bias into one fma.  A hidden activation past
+// 65504 / 2^3 overflows the hi part: the range guard reports it.
 constexpr float kActS = 8.0f;
 constexpr float kWS = 64.0f;
 

@@ -9,10 +9,6 @@
 #include "aon_common.hpp"
 #include "mlp_layout.hpp"
 
-#ifndef AON_DMA_ASM
-#define AON_DMA_ASM 1
-#endif
-
 namespace aon {
 namespace mlp {
 
@@ -140,7 +136,6 @@ struct DmaPipe {
   __device__ __forceinline__ void issue(int c) {
 #pragma unroll
     for (int i = 0; i < kCopies; ++i) {
-#if AON_DMA_ASM
       // Opaque to the compiler: with a visible LDS-DMA in flight hipcc drains lgkmcnt to 0
       // before every ds_read (defeating the fragment prefetch); hidden, it keeps counted
       // lgkmcnt(N) waits.  Ordering is ours: begin() waits vmcnt for this wave's copies and
@@ -158,15 +153,6 @@ struct DmaPipe {
                    : "s"(m0), "v"(voff), "s"(gbase)
                    : "memory", "m0");
 #pragma clang diagnostic pop
-#else
-      f4* dst = wbuf + (c % NBUF) * kChunk * 64;
-      const int e = i * THREADS + tid;  // 16-B element of the chunk; LDS dst is lane-linear
-      __builtin_amdgcn_global_load_lds(
-          reinterpret_cast<const void*>(src + (size_t)c * kChunk * 64 + e),
-          reinterpret_cast<__attribute__((address_space(3))) void*>(
-              reinterpret_cast<uintptr_t>(dst + e - lane)),
-          16, 0, 0);
-#endif
     }
   }
   __device__ __forceinline__ void start() {

@@ -17,8 +17,8 @@ namespace aon {
 // A ray's inputs -- its t_merge row (or bins), weights and u, NBX 64-entry blocks of each -- are
 // read by coalesced wave-wide loads, all issued before any math, and staged in LDS (the weight
 // sum reads LDS, not HBM).  One ray per wave on a grid of up to 65,536 workgroups: many short
-// waves hide HBM latency better than AON_PDF_PIPE's resident grid with ray r + 1's loads issued
-// before ray r's math (measured 0.40 vs 0.43 ms per frame).
+// waves hide HBM latency better than a resident grid with ray r + 1's loads issued before ray
+// r's math (measured 0.40 vs 0.43 ms per frame).
 template <int NBX>
 __global__ __launch_bounds__(64 * kPdfWaves) void k_sample_pdf(
     const float* __restrict__ bins_g, int64_t bins_stride, const float* __restrict__ w_g,
@@ -30,9 +30,8 @@ __global__ __launch_bounds__(64 * kPdfWaves) void k_sample_pdf(
   PdfLds<NBX>& L = lds_all[wid];
   const int nw = nb - 1;
   const int64_t nwaves = (int64_t)gridDim.x * kPdfWaves;
-  // this lane's entries 64 b + lane of t_merge, bins, weights and u: current ray, next ray
+  // this lane's entries 64 b + lane of t_merge, bins, weights and u
   float ct[NBX], cb[NBX], cw[NBX], cu[NBX];
-  float pt[NBX], pb[NBX], pw[NBX], pu[NBX];
   auto load_ray = [&](int64_t r, float(&tv)[NBX], float(&bv)[NBX], float(&wv)[NBX],
                       float(&uv)[NBX]) {
 #pragma unroll
@@ -45,12 +44,8 @@ __global__ __launch_bounds__(64 * kPdfWaves) void k_sample_pdf(
     }
   };
   int64_t ray = (int64_t)blockIdx.x * kPdfWaves + wid;
-  if (AON_PDF_PIPE && ray < B) load_ray(ray, ct, cb, cw, cu);
   for (; ray < B; ray += nwaves) {
-    if (!AON_PDF_PIPE)
-      load_ray(ray, ct, cb, cw, cu);
-    else if (ray + nwaves < B)
-      load_ray(ray + nwaves, pt, pb, pw, pu);
+    load_ray(ray, ct, cb, cw, cu);
     // ---- stage t_merge, bins and the weights
 #pragma unroll
     for (int b = 0; b < NBX; ++b) {
@@ -66,15 +61,6 @@ __global__ __launch_bounds__(64 * kPdfWaves) void k_sample_pdf(
     pdf_ray<NBX>(L, L.w, nb, Ns, Ns_pow2, cu, tm_g != nullptr, Nt, ray, lane,
                  out + ray * (tm_g ? Nt + Ns : Ns), xyz, ro, rd);
     wave_sync();  // LDS reuse by the next ray of this wave
-    if (AON_PDF_PIPE) {
-#pragma unroll
-    for (int b = 0; b < NBX; ++b) {
-      ct[b] = pt[b];
-      cb[b] = pb[b];
-      cw[b] = pw[b];
-      cu[b] = pu[b];
-    }
-    }
   }
 }
 
@@ -83,9 +69,7 @@ static void launch_pdf(hipStream_t st, const float* bins, int64_t bins_stride, c
                        int64_t w_stride, int64_t B, int nb, int Ns, int p2, const float* u,
                        int64_t u_stride, const float* tm, int Nt, const float* ro,
                        const float* rd, float* out, float* xyz) {
-  const int grid = AON_PDF_PIPE
-                       ? resident_grid(k_sample_pdf<NBX>, 64 * kPdfWaves, (B + kPdfWaves - 1) / kPdfWaves)
-                       : grid_for(B, kPdfWaves, 1 << 16);
+  const int grid = grid_for(B, kPdfWaves, 1 << 16);
   hipLaunchKernelGGL(k_sample_pdf<NBX>, grid, 64 * kPdfWaves, 0, st, bins, bins_stride, w,
                      w_stride, B, nb, Ns, p2, u, u_stride, tm, Nt, ro, rd, out, xyz);
 }

@@ -7,10 +7,6 @@
 
 namespace aon {
 
-#ifndef AON_PDF_PIPE
-#define AON_PDF_PIPE 0  // 1: next ray's inputs loaded one ray ahead on a resident grid (7% slower)
-#endif
-
 constexpr int kPdfWaves = 4;
 constexpr int kMaxBins = 256;
 constexpr int kMaxNs = 512;
@@ -22,34 +18,9 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_wave_barrier();
 }
 
-// Two-level counts in a sorted LDS row, 2 dependent LDS round trips instead of log2(n): the
-// every-8th "pivots" a[8m + 7] (the same address on every lane: broadcast reads) give the first
-// bucket q whose pivot is not counted; buckets before it count whole, bucket q entry by entry,
-// everything after it is past x (sorted).  Equal to the binary searches below for any x
-// (NaN x: 0; +inf entries sort last).
-template <bool LE>
-__device__ __forceinline__ int count_sorted(const float* a, int n, float x) {
-  const int nfull = n >> 3;
-  int q = 0;
-  for (int m = 0; m < nfull; ++m) {
-    const float p = a[8 * m + 7];
-    q += LE ? (p <= x) : (p < x);
-  }
-  int c = 8 * q;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const int i = 8 * q + e;
-    if (i < n) {
-      const float v = a[i];
-      c += LE ? (v <= x) : (v < x);
-    }
-  }
-  return c;
-}
-
 // Branch-free binary lifting: the largest c with a[c-1] <= x (LE) / < x, one probe per power of
-// two below n -- a trip count uniform across the wave (no divergent loop exits).  Equal to the
-// while-loop searches below on sorted rows (NaN x: 0).
+// two below n -- a trip count uniform across the wave (no divergent loop exits).  Equal to a
+// binary search on sorted rows (NaN x: 0; +inf entries sort last).
 template <bool LE>
 __device__ __forceinline__ int count_lift(const float* a, int n, float x) {
   int c = 0;
@@ -63,46 +34,13 @@ __device__ __forceinline__ int count_lift(const float* a, int n, float x) {
   return c;
 }
 
-#ifndef AON_PDF_SEARCH2
-#define AON_PDF_SEARCH2 2  // 2: count_lift (fused march 0.418 -> 0.394 ms); 1: two-level searches (more LDS reads: 5-15% slower); 0: while-loop binary searches (profiles/r02/ab_march)
-#endif
-
-// number of entries of sorted a[0..n) that are <= x  (upper bound)
-__device__ __forceinline__ int count_le_bin(const float* a, int n, float x) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (a[mid] <= x) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
-// number of entries of sorted a[0..n) that are < x  (lower bound)
-__device__ __forceinline__ int count_lt_bin(const float* a, int n, float x) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (a[mid] < x) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
+// number of entries of sorted a[0..n) that are <= x (upper bound) / < x (lower bound)
 __device__ __forceinline__ int count_le(const float* a, int n, float x) {
-  return AON_PDF_SEARCH2 == 2 ? count_lift<true>(a, n, x)
-         : AON_PDF_SEARCH2 ? count_sorted<true>(a, n, x) : count_le_bin(a, n, x);
+  return count_lift<true>(a, n, x);
 }
 __device__ __forceinline__ int count_lt(const float* a, int n, float x) {
-  return AON_PDF_SEARCH2 == 2 ? count_lift<false>(a, n, x)
-         : AON_PDF_SEARCH2 ? count_sorted<false>(a, n, x) : count_lt_bin(a, n, x);
+  return count_lift<false>(a, n, x);
 }
-
-#ifndef AON_PDF_HINT_MERGE
-#define AON_PDF_HINT_MERGE 1  // 0: merge by binary searches on both sides
-#endif
-
-#ifndef AON_PDF_DPP_SCAN
-#define AON_PDF_DPP_SCAN 1  // 0: the shuffle (ds_bpermute) scan
-#endif
 
 // per-wave LDS, sized for rows of up to 64 * NBX entries (bins, weights, samples, t_merge)
 template <int NBX>
@@ -151,15 +89,7 @@ __device__ __forceinline__ void pdf_ray(PdfLds<NBX>& L, const float* w, int nb, 
     const int k = base + lane;
     double v = 0.0;
     if (k < nw - 1) v = (double)__fdiv_rn(__fadd_rn(w[k], padw), wsum);
-#if AON_PDF_DPP_SCAN
     v = wave_incl_sum(v);  // DPP lane moves, no LDS round trips
-#else
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const double x = __shfl_up(v, o);
-      if (lane >= o) v += x;
-    }
-#endif
     if (k < nw - 1) L.cdf[k + 1] = fminf(1.0f, (float)(carry + v));
     carry += readlane_f64(v, 63);
   }
@@ -221,7 +151,6 @@ __device__ __forceinline__ void pdf_ray(PdfLds<NBX>& L, const float* w, int nb, 
     dx = rd[3 * ray]; dy = rd[3 * ray + 1]; dz = rd[3 * ray + 2];
   }
   float* xo = xyz ? xyz + ray * No * 3 : nullptr;
-#if AON_PDF_HINT_MERGE
   if (merge && !need_sort) {
     // Samples in u order are ascending: sample j's bin i0 bounds its rank in t_merge from below
     // (t_merge[i0] <= bins[i0] <= sample, bins = mids of t_merge), and it lies below
@@ -274,7 +203,6 @@ __device__ __forceinline__ void pdf_ray(PdfLds<NBX>& L, const float* w, int nb, 
     }
     return;
   }
-#endif
   for (int j = lane; j < Ns; j += 64) {
     const float s = L.samp[j];
     const int pos = merge ? j + count_le(L.tm, Nt, s) : j;

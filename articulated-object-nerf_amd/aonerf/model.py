@@ -28,6 +28,7 @@ import torch.nn.init as init
 
 from . import _lib as L
 from . import helper
+from .level import composite_fwd, events as _events, record as _record
 from .numerics import resolve as _resolve_numerics
 
 _DEFAULT_GEOMETRY = dict(min_deg_point=0, max_deg_point=10, deg_view=4, netdepth=8, netwidth=256,
@@ -150,21 +151,6 @@ class NeRFMLP(nn.Module):
                L.stream(x.device))
         raw = raw.view(B, S, 4)
         return raw[..., :3], raw[..., 3:]
-
-
-def _events(timers):
-    """HIP events bracketing one launch on the current stream (the stream the C ABI uses)."""
-    if timers is None:
-        return None
-    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-    ev[0].record()
-    return ev
-
-
-def _record(timers, ev, key, rows):
-    if ev is not None:
-        ev[1].record()
-        timers.setdefault(key, []).append((ev[0], ev[1], rows))
 
 
 def fine_uniforms(B, num_fine_samples, randomized, dev, u_fine=None):
@@ -395,12 +381,6 @@ class NeRF(nn.Module):
                 raw, t_vals, d, white_bkgd, act, u, u_stride, self.num_fine_samples, keep_weights)
             _record(timers, ev, f"march{level}", B * S)
         else:
-            comp = torch.empty((B, 3), device=dev)
-            acc = torch.empty((B,), device=dev)
-            weights = torch.empty((B, S), device=dev) if keep_weights else None
-            depth = torch.empty((B,), device=dev)
-            L.call("aon_composite_fwd", L.ptr(raw), 4, L.ptr(raw[:, 3:]), 4, L.ptr(t_vals), L.ptr(d),
-                   B, S, int(bool(white_bkgd)), act, L.ptr(comp), L.ptr(acc), L.ptr(weights),
-                   L.ptr(depth), L.stream(dev))
+            comp, acc, depth, weights = composite_fwd(raw, t_vals, d, white_bkgd, act, keep_weights)
             _record(timers, ev, f"comp{level}", B * S)
         return (comp, acc, depth, weights, dict(t_vals=t_vals, weights=weights, rgb_sigma=raw)), weights, t_next

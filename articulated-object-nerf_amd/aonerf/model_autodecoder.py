@@ -18,9 +18,9 @@ then the coarse compositor fused with the fine level's resampling (aon_composite
 the fine level, aon_composite_fwd (AON_ACT_ARTIC; :324-333).  The latent codes are the same for
 every sample (the reference repeats (1, C) rows over all B*S rows, :186-194), so their products
 with the weight columns they meet are folded into per-call biases (b' = b + W[:, latent cols] .
-latent, one tiny GEMM each).  ``NeRFMLP.fused = False`` selects the layer-by-layer path, every
-product on the f16x3 MFMA GEMM (aon_gemm), which is also the fallback when an activation leaves
-the fused kernel's fp16x3 range.  No torch arithmetic on the path.
+latent, one tiny GEMM each).  ``NeRFMLP.fused = False`` selects the layer-by-layer path
+(level.art_forward, the walker the training path shares), every product on the f16x3 MFMA GEMM
+(aon_gemm): also the fallback when an activation leaves the fused kernel's fp16x3 range.
 """
 import warnings
 
@@ -29,7 +29,7 @@ import torch.nn as nn
 import torch.nn.init as init
 
 from . import _lib as L
-from .linalg import ACT_SCALE, W_SCALE, gemm, linear_fwd
+from . import level as _level
 from .model import _events, _record, composite_march, fine_uniforms, level_t_vals, march_ok
 from .numerics import resolve as _resolve_numerics
 
@@ -92,51 +92,38 @@ class NeRFMLP(nn.Module):
             init.xavier_uniform_(m.weight)
         self.pos_size_enc = pos_size - shape_latent_dim  # 63
 
-    # -- latent folding: b' = b + W[:, c0:c0+n] . latent (one M=1 GEMM with bias epilogue)
-    @staticmethod
-    def _fold(layer, c0, latent):
-        W = layer.weight.detach()
-        out = torch.empty((1, W.shape[0]), device=W.device)
-        n = latent.shape[-1]
-        gemm(out, latent, W[:, c0:], 1, W.shape[0], n, lda=n, a_kc=True, ldb=W.shape[1], b_kc=True,
-             ldc=W.shape[0], bias=layer.bias.detach(), a_scale=1.0, b_scale=W_SCALE)
-        return out.reshape(-1)
+    # -- latent folding: b' = b + W[:, c0:c0+n] . latent (_level.fold)
+    def _pairs(self):
+        """(weight, bias) in the kernels' layer order (contiguous copies, if any, live here)."""
+        return [(L.contig(m.weight.detach()), L.contig(m.bias.detach()))
+                for m in _level.art_layers(self)]
 
-    def folded_biases(self, latents):
+    def _folded(self, P, latents):
         shape = L.contig(latents["density"].detach().reshape(1, -1))
         app = L.contig(latents["color"].detach().reshape(1, -1))
         art = L.contig(latents["articulation"].detach().reshape(1, -1))
         L.require_gpu(shape, app, art)
         if shape.shape[1] != self.shape_latent_dim or art.shape[1] != self.articulation_latent_dim:
             raise ValueError("latent code sizes do not match the MLP")
-        lat_def = torch.cat([shape, art], -1)  # the 160 latent columns of cat[pos, shape, art]
-        return {
-            "def0": self._fold(self.deformations_linear[0], self.input_ch, lat_def),
-            "pts0": self._fold(self.pts_linears[0], self.pos_size_enc, shape),
-            "pts_skip": self._fold(self.pts_linears[self.skip_layer + 1],
-                                   self.netwidth + self.pos_size_enc, shape),
-            "view0": self._fold(self.views_linear[0],
-                                self.netwidth + (self.deg_view * 2 + 1) * self.input_ch_view, app),
-        }
+        # lat_def: the 160 latent columns of cat[pos, shape, art], held over the four folds
+        return _level.folded_biases(_level.geo_of(self), P, (shape, app, art),
+                                   lat_def=torch.cat([shape, art], -1))
+
+    def folded_biases(self, latents):
+        geo = _level.geo_of(self)
+        fb = self._folded(self._pairs(), latents)
+        return {"def0": fb[geo.DEF0], "pts0": fb[geo.PTS0], "pts_skip": fb[geo.PTS0 + geo.skip],
+                "view0": fb[geo.VIEW0]}
 
     @torch.no_grad()
     def packed_weights(self, latents):
         """The fused kernel's fp16x3 weight stream with this call's folded biases
         (aon_mlp_art_pack; re-packed per call: the folded biases follow the latent codes)."""
-        fb = self.folded_biases(latents)
-        W = lambda m: L.contig(m.weight.detach())  # noqa: E731
-        b = lambda m: L.contig(m.bias.detach())  # noqa: E731
-        # (weight, bias) in the kernels' layer order; contiguous copies (if any) live in `pairs`
-        # until the pack is enqueued
-        pairs = [(W(m), fb["def0"] if i == 0 else b(m)) for i, m in enumerate(self.deformations_linear)]
-        pairs.append((W(self.deformation_layer), b(self.deformation_layer)))
-        pairs += [(W(m), fb["pts0"] if i == 0 else fb["pts_skip"] if i == self.skip_layer + 1
-                   else b(m)) for i, m in enumerate(self.pts_linears)]
-        pairs += [(W(self.density_layer), b(self.density_layer)),
-                  (W(self.bottleneck_layer), b(self.bottleneck_layer))]
-        pairs += [(W(m), fb["view0"] if i == 0 else b(m)) for i, m in enumerate(self.views_linear)]
-        pairs.append((W(self.rgb_layer), b(self.rgb_layer)))
-        prm = L.mlp_art_params(pairs)  # shape-checked (ValueError) before the pack
+        P = self._pairs()
+        # the folded biases live in `pairs` until the pack is enqueued (the struct holds plain
+        # pointers); shape-checked (ValueError) before the pack
+        pairs = _level.folded_pairs(P, self._folded(P, latents))
+        prm = L.mlp_art_params(pairs)
         dev = self.rgb_layer.weight.device
         nbytes = L.lib().aon_mlp_art_packed_bytes()
         buf = getattr(self, "_art_packed", None)
@@ -147,13 +134,8 @@ class NeRFMLP(nn.Module):
         return buf
 
     def _fused_ok(self):
-        # the fused kernel is compiled for the default geometry (mlp_layout.hpp kLayersArt)
-        return (self.fused and self.netdepth == 8 and self.netwidth == 256 and self.skip_layer == 4
-                and self.netdepth_deformation == 4 and self.netwidth_deformation == 128
-                and self.netdepth_condition == 4 and self.netwidth_condition == 128
-                and self.input_ch == 3 and self.input_ch_view == 3 and self.min_deg_point == 0
-                and self.max_deg_point == 10 and self.deg_view == 4
-                and self.num_rgb_channels == 3 and self.num_density_channels == 1)
+        # the fused kernel is compiled for the default geometry (_level.Geo.fused_ok)
+        return self.fused and _level.geo_of(self).fused_ok
 
     @torch.no_grad()
     def forward_rays(self, rays_o, rays_d, viewdirs, t_vals, latents, act=L.ACT_NONE):
@@ -181,61 +163,13 @@ class NeRFMLP(nn.Module):
 
     @torch.no_grad()
     def _mlp(self, xyz, venc, S, latents):
-        """The MLP on sample positions xyz (R, 3), view encodings venc (R / S, 27) -> (R, 4)."""
-        R, dev = xyz.shape[0], xyz.device
-        fb = self.folded_biases(latents)
-        W = lambda m: m.weight.detach()  # noqa: E731
-        b = lambda m: m.bias.detach()  # noqa: E731
-        # deformation MLP (model_autodecoder.py:196-205); layer 0 sees only xyz per sample
-        wd = self.netwidth_deformation
-        h = torch.empty((R, wd), device=dev)
-        h2 = torch.empty((R, wd), device=dev)
-        d0 = self.deformations_linear[0]
-        gemm(h, xyz, W(d0), R, wd, 3, lda=3, a_kc=True, ldb=W(d0).shape[1], b_kc=True, ldc=wd,
-             bias=fb["def0"], relu=True, a_scale=ACT_SCALE, b_scale=W_SCALE)
-        for m in list(self.deformations_linear)[1:]:
-            linear_fwd(h2, h, wd, W(m), b(m), relu=True)
-            h, h2 = h2, h
-        delta = torch.empty((R, 3), device=dev)
-        linear_fwd(delta, h, wd, W(self.deformation_layer), b(self.deformation_layer))
-        del h, h2
-        # x' = deformation + xyz, then pos_enc (enc_after, :205-212), points given directly
-        enc = torch.empty((R, self.pos_size_enc), device=dev)
-        L.call("aon_cast_rays", L.ptr(xyz), None, None, R, 1, L.ptr(delta), 3, None,
-               self.min_deg_point, self.max_deg_point, L.ptr(enc), L.stream(dev))
-        # trunk on inputs = cat[enc, shape] (:214-220), shape folded into the biases
-        nw, ne = self.netwidth, self.pos_size_enc
-        x = torch.empty((R, nw), device=dev)
-        y = torch.empty((R, nw), device=dev)
-        p0 = self.pts_linears[0]
-        gemm(x, enc, W(p0), R, nw, ne, lda=ne, a_kc=True, ldb=W(p0).shape[1], b_kc=True, ldc=nw,
-             bias=fb["pts0"], relu=True, a_scale=ACT_SCALE, b_scale=W_SCALE)
-        for idx in range(1, self.netdepth):
-            m = self.pts_linears[idx]
-            if idx == self.skip_layer + 1:  # cat[h, enc, shape]
-                gemm(y, x, W(m), R, nw, nw + ne, lda=nw, a_kc=True, ldb=W(m).shape[1], b_kc=True,
-                     ldc=nw, A2=enc, lda2=ne, K1=nw, bias=fb["pts_skip"], relu=True,
-                     a_scale=ACT_SCALE, b_scale=W_SCALE)
-            else:
-                linear_fwd(y, x, nw, W(m), b(m), relu=True)
-            x, y = y, x
-        raw = torch.empty((R, 4), device=dev)
-        linear_fwd(raw[:, 3:], x, nw, W(self.density_layer), b(self.density_layer), ldo=4)
-        bot = y
-        linear_fwd(bot, x, nw, W(self.bottleneck_layer), b(self.bottleneck_layer))
-        # view branch on cat[bottleneck, enc_dir tiled over samples, appearance] (:224-235)
-        wc, nv = self.netwidth_condition, venc.shape[1]
-        v0 = self.views_linear[0]
-        hv = torch.empty((R, wc), device=dev)
-        hv2 = torch.empty((R, wc), device=dev)
-        gemm(hv, bot, W(v0), R, wc, nw + nv, lda=nw, a_kc=True, ldb=W(v0).shape[1], b_kc=True,
-             ldc=wc, A2=venc, lda2=nv, K1=nw, a2_rdiv=S, bias=fb["view0"], relu=True,
-             a_scale=ACT_SCALE, b_scale=W_SCALE)
-        for m in list(self.views_linear)[1:]:
-            linear_fwd(hv2, hv, wc, W(m), b(m), relu=True)
-            hv, hv2 = hv2, hv
-        linear_fwd(raw, hv, wc, W(self.rgb_layer), b(self.rgb_layer), ldo=4)
-        return raw
+        """The MLP on sample positions xyz (R, 3), view encodings venc (R / S, 27) -> (R, 4):
+        _level.art_forward on two alternating buffers per width."""
+        geo = _level.geo_of(self)
+        P = self._pairs()
+        fb = self._folded(P, latents)
+        bufs = _level.LayerBuffers(geo, xyz.shape[0], xyz.device)
+        return _level.art_forward(geo, P, fb.__getitem__, xyz, venc, S, bufs)[1]
 
     def forward(self, pos, condition, latents):
         """reference model_autodecoder.py:168-239: pos (B, S, 3) sample positions (enc_after),
@@ -360,13 +294,8 @@ class NeRF_AE_Art(nn.Module):  # noqa: N801 (reference name)
                     return_weights or return_intermediates)
                 _record(timers, ev, f"march{level}", B * S)
             else:
-                comp = torch.empty((B, 3), device=dev)
-                acc = torch.empty((B,), device=dev)
-                weights = torch.empty((B, S), device=dev)
-                depth = torch.empty((B,), device=dev)
-                L.call("aon_composite_fwd", L.ptr(raw), 4, L.ptr(raw[:, 3:]), 4, L.ptr(t_vals),
-                       L.ptr(d), B, S, int(bool(white_bkgd)), L.ACT_ARTIC, L.ptr(comp), L.ptr(acc),
-                       L.ptr(weights), L.ptr(depth), L.stream(dev))
+                comp, acc, depth, weights = _level.composite_fwd(raw, t_vals, d, white_bkgd,
+                                                                L.ACT_ARTIC)
                 _record(timers, ev, f"comp{level}", B * S)
             out = (comp, acc, depth, weights) if return_weights else (comp, acc, depth)
             if return_intermediates:

@@ -13,7 +13,9 @@ One render level under autograd is ``RenderLevel`` (a torch.autograd.Function):
 
 (The model's TrainNumerics -- aonerf/numerics.py, per model -- with fused_forward /
 fused_backward False selects the layer-by-layer aon_gemm forward and backward that the fused
-kernels replaced; both are gated identically in tests/test_gpu_train.py.)
+kernels replaced; both are gated identically in tests/test_gpu_train.py.)  What a level
+shares with the articulated one (train_art.py) -- timers, the pack-buffer cache, the compositor
+calls, the weight-gradient operands' aon_gemm keywords, the all-GEMM products -- is level.py.
 
 Gradients land in each parameter's ``.grad`` through autograd, so the reference's own
 optimizer code runs unchanged (the fp16x3 range guard reaches it through a global
@@ -22,13 +24,14 @@ reference's learning-rate schedule.  All arithmetic is in the HIP kernels; torch
 allocates buffers and routes autograd.
 """
 import contextlib
+import functools
 
 import numpy as np
 import torch
 import torch.optim.optimizer as _torch_optim
 
 from . import _lib as L
-from . import tiles
+from . import level, tiles
 
 from .linalg import ACT_SCALE, GRAD_SCALE, W_SCALE, batched, colsum, gemm, linear_fwd  # noqa: F401
 from .numerics import DEFAULT, TrainNumerics  # noqa: F401
@@ -73,75 +76,52 @@ def _backward_level(P, G, enc, venc, S, h, bot, hv, draw):
     max |dY| (aon_absmax -> aon_gemm a_amax), as the fused chain scales its d raw: a fixed
     prescale would push the small dL/dz of a late-training step into fp16's subnormals."""
     R, dev = enc.shape[0], enc.device
-    acts = ACT_SCALE
     words = torch.zeros((8,), dtype=torch.int32, device=dev)
 
-    def dweight(dW, dY, ldy, n_out, X, ldx, n_in, rdiv=1, col0=0, ldw=None, db=None, amax=None):
-        # dW[:, col0:col0+n_in] = dY^T X (K = rows, split over workgroups); db = sum_rows dY
-        # from the same pass over dY
-        gemm(dW[:, col0:] if col0 else dW, dY, X, n_out, n_in, R, lda=ldy, a_kc=False, ldb=ldx,
-             b_kc=False, b_rdiv=rdiv, ldc=ldw or dW.shape[1], a_scale=1.0, b_scale=acts,
-             rowsum=db, a_amax=amax)
+    def dweight(i, dY, ldy, X, ldx, n_in, amax, col0=0, rdiv=1, bias=True):
+        level.gemm_dweight(G[i][0], G[i][1] if bias else None, dY, ldy, X, ldx, n_in, R,
+                           col0=col0, rdiv=rdiv, amax=amax)
 
-    def dinput(dX, dY, ldy, n_out, W, n_in, mask=None, accumulate=False, amax=None):
-        # dX (R x n_in) = dY W[:, :n_in] (* relu mask)
-        gemm(dX, dY, W, R, n_in, n_out, lda=ldy, a_kc=True, ldb=W.shape[1], b_kc=False,
-             ldc=dX.shape[1], mask=mask, ldm=mask.shape[1] if mask is not None else 0,
-             accumulate=accumulate, a_scale=1.0, b_scale=W_SCALE, a_amax=amax)
+    def dinput(dX, dY, ldy, i, n_in, amax, mask=None, accumulate=False):
+        level.gemm_dinput(dX, dY, ldy, P[i][0], n_in, R, mask=mask, accumulate=accumulate,
+                          amax=amax)
 
     # rgb head (N=3) and view layer
     wd = _amax_word(draw, words[0:1])  # d raw (its sigma column too: a max over both is safe)
-    dweight(G[11][0], draw, 4, 3, hv, 128, 128, db=G[11][1], amax=wd)
+    dweight(11, draw, 4, hv, 128, 128, wd)
     dhv = torch.empty((R, 128), device=dev)
-    dinput(dhv, draw, 4, 3, P[11][0], 128, mask=hv, amax=wd)
+    dinput(dhv, draw, 4, 11, 128, wd, mask=hv)
     wv = _amax_word(dhv, words[1:2])
-    dweight(G[10][0], dhv, 128, 128, bot, 256, 256, db=G[10][1], amax=wv)
-    dweight(G[10][0], dhv, 128, 128, venc, 27, 27, rdiv=S, col0=256, amax=wv)
+    dweight(10, dhv, 128, bot, 256, 256, wv)
+    dweight(10, dhv, 128, venc, 27, 27, wv, col0=256, rdiv=S, bias=False)
     dbot = torch.empty((R, 256), device=dev)
-    dinput(dbot, dhv, 128, 128, P[10][0], 256, amax=wv)
+    dinput(dbot, dhv, 128, 10, 256, wv)
     del dhv
     # bottleneck + density heads on h7
     wb = _amax_word(dbot, words[2:3])
-    dweight(G[9][0], dbot, 256, 256, h[7], 256, 256, db=G[9][1], amax=wb)
-    dweight(G[8][0], draw[:, 3:], 4, 1, h[7], 256, 256, db=G[8][1], amax=wd)
+    dweight(9, dbot, 256, h[7], 256, 256, wb)
+    dweight(8, draw[:, 3:], 4, h[7], 256, 256, wd)
     dy = torch.empty((R, 256), device=dev)
-    dinput(dy, dbot, 256, 256, P[9][0], 256, amax=wb)
-    dinput(dy, draw[:, 3:], 4, 1, P[8][0], 256, mask=h[7], accumulate=True, amax=wd)
+    dinput(dy, dbot, 256, 9, 256, wb)
+    dinput(dy, draw[:, 3:], 4, 8, 256, wd, mask=h[7], accumulate=True)
     del dbot
     dx = torch.empty((R, 256), device=dev)
     for i in range(7, -1, -1):  # dy = dL/d(pre-activation of layer i)
         wy = _amax_word(dy, words[3 + (i & 1):4 + (i & 1)])
+        if i == 0:
+            dweight(0, dy, 256, enc, 63, 63, wy)
+            break
+        dweight(i, dy, 256, h[i - 1], 256, 256, wy)
         if i == 5:
-            dweight(G[5][0], dy, 256, 256, h[4], 256, 256, db=G[5][1], amax=wy)
-            dweight(G[5][0], dy, 256, 256, enc, 63, 63, col0=256, amax=wy)
-        elif i == 0:
-            dweight(G[0][0], dy, 256, 256, enc, 63, 63, db=G[0][1], amax=wy)
-        else:
-            dweight(G[i][0], dy, 256, 256, h[i - 1], 256, 256, db=G[i][1], amax=wy)
-        if i > 0:
-            dinput(dx, dy, 256, 256, P[i][0], 256, mask=h[i - 1], amax=wy)
-            dx, dy = dy, dx
+            dweight(5, dy, 256, enc, 63, 63, wy, col0=256, bias=False)
+        dinput(dx, dy, 256, i, 256, wy, mask=h[i - 1])
+        dx, dy = dy, dx
 
 
 # Which kernels and precision a level trains with is the MODEL's TrainNumerics
 # (aonerf/numerics.py; NeRF(train_precision=...)), passed into RenderLevel per call -- no
 # module-level switch.  ``timers`` (a dict, optional, per call) -> hip events around each level's
 # training kernels (bench.py's train_step roofline): "fwd_train<S>", "bwd_chain<S>", "dweight<S>".
-
-
-def _ev(timers):
-    if timers is None:
-        return None
-    e = torch.cuda.Event(enable_timing=True)
-    e.record()
-    return e
-
-
-def _rec(timers, key, e0, rows):
-    if e0 is not None:
-        e1 = torch.cuda.Event(enable_timing=True)
-        e1.record()
-        timers.setdefault(key, []).append((e0, e1, rows))
 
 
 class JoinToken:
@@ -201,28 +181,11 @@ def _on_side(token, dev, tensors):
     token.pending.append((main, ev))
 
 
-_packed = {}
-
-
 def _params_struct(P):
-    """AonMlpParams of one level's (weight, bias) pairs in the kernels' layer order (pts_linears.0
-    ..7, density, bottleneck, views_linear.0, rgb): shapes, dtype, device and contiguity are
-    checked against the layer table (ValueError) before any pointer reaches a pack kernel, and
-    the C side checks the shapes again (aon_mlp_params, ABI 9)."""
+    """AonMlpParams of one level's (weight, bias) pairs in the kernels' layer order: checked
+    against the layer table (ValueError) before any pointer reaches a pack kernel, and again by
+    the C side (aon_mlp_params, ABI 9)."""
     return L.mlp_params(P)
-
-
-def _buffer(key, nbytes, dev, guard=False, params=()):
-    # one buffer per kind and device: a pack and the kernel reading it are stream-ordered.
-    # guard: a packed weight stream whose range-status word the next optimizer step over
-    # ``params`` (the packed parameters) checks
-    buf = _packed.get((key, str(dev)))
-    if buf is None:
-        buf = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=dev)
-        _packed[(key, str(dev))] = buf
-    if guard:
-        L.register_pack(("train", key), buf, params)
-    return buf
 
 
 # an optimizer step refuses gradients whose kernels met a fp16x3 range overflow (one sync per
@@ -264,19 +227,17 @@ def _pack(P, dev, tag="", bf16=False):
     optimizer updates the parameters in place behind torch's version counters).  ``tag``: one
     buffer per level (its range-status word must survive until the optimizer step)."""
     prec = L.PREC_BF16 if bf16 else L.PREC_F16X3_TRAIN
-    buf = _buffer(f"fwd{'bf' if bf16 else ''}{tag}", L.lib().aon_mlp_packed_bytes(prec), dev,
-                  guard=not bf16, params=[t for wb in P for t in wb])
+    buf = level.buffer("train", f"fwd{'bf' if bf16 else ''}{tag}",
+                       L.lib().aon_mlp_packed_bytes(prec), dev, guard=not bf16,
+                       params=[t for wb in P for t in wb])
     L.call("aon_mlp_pack", L.ctypes.byref(_params_struct(P)), prec, L.ptr(buf), L.stream(dev))
     return buf
 
 
 def _pack_bwd(P, dev, tag="", bf16=False):
     """The transposed weight stream of the fused backward chain (aon_mlp_bwd_pack[_bf16])."""
-    buf = _buffer(f"bwd{'bf' if bf16 else ''}{tag}", L.lib().aon_mlp_bwd_packed_bytes(), dev,
-                  guard=not bf16, params=[t for wb in P for t in wb])
-    L.call("aon_mlp_bwd_pack_bf16" if bf16 else "aon_mlp_bwd_pack",
-           L.ctypes.byref(_params_struct(P)), L.ptr(buf), L.stream(dev))
-    return buf
+    return level.pack_bwd("train", "aon_mlp_bwd_pack", L.lib().aon_mlp_bwd_packed_bytes,
+                          _params_struct, P, dev, tag, bf16)
 
 
 def relu_masks(acts, R):
@@ -312,59 +273,40 @@ def _backward_level_fused(P, G, enc, venc, S, h, bot, hv, draw, masks=None, h_ti
     dz = torch.empty((8, NR, 256), device=dev, dtype=dt)
     # the chain's d raw scale word: the weight gradients read it, on the side stream while the
     # next level's chain may already run -- its own word then
-    work = _buffer("work", 4, dev) if token is None else torch.empty((1,), device=dev)
+    work = level.buffer("train", "work", 4, dev) if token is None else torch.empty((1,), device=dev)
     packed = _pack_bwd(P, dev, S, bf16)
-    e0 = _ev(timers)
+    ev = level.events(timers)
     L.call("aon_mlp_bwd_bf16" if bf16 else "aon_mlp_bwd", L.ptr(packed), L.ptr(draw), L.ptr(masks),
            R, L.ptr(dzv), L.ptr(dzb), L.ptr(dz), L.ptr(work), L.stream(dev))
     L.snapshot_pack(packed)  # the chain was the pack's last reader (range guard, _lib)
-    _rec(timers, f"bwd_chain{S}", e0, R)
-    e0 = _ev(timers)
-    acts = ACT_SCALE
+    level.record(timers, ev, f"bwd_chain{S}", R)
+    ev = level.events(timers)
 
-    # the tiled copy of pos_enc(x): the bf16 forward's (NR, 128) bf16 or the f16x3 mode's
-    # (NR, 64) fp32 (aon_cast_rays_tiled); else row-major (R, 63)
-    enc_t = enc.shape[1] != 63
+    # the operands (level.Operand): d raw row-major, the chain's dzv / dzb / dz tiled, the kept
+    # activations tiled after the fused forward, pos_enc(x) as the forward kept it
+    Op = level.Operand
+    (d_raw, d_sigma), d_zv = level.draw_operands(draw), Op(dzv, 128, True, level.CHAIN)
+    d_zb, *d_z = level.operands((dzb, *dz.unbind(0)), 256, True, level.CHAIN)
+    x_bot, *x_h = level.operands((bot, *h), 256, h_tiled, level.ACT)
+    x_hv, x_venc = Op(hv, 128, h_tiled, level.ACT), Op(venc, 27, False, level.VENC)
+    x_enc = level.enc_operand(enc)
 
-    def dweight(dW, dY, ldy, n_out, X, ldx, n_in, rdiv=1, col0=0, db=None, a_t=True):
-        # f16x3: dY rides at the chain's own per-call scale from max |d raw| (the word in
-        # `work`); bf16: one bf16 MFMA per product, no scales needed.  dY: the chain's tiled
-        # gradients (a_t) or row-major d raw; X: a kept activation (tiled when h_tiled), the
-        # encodings (row-major (R, 63), or the bf16 forward's tiled (NR, 128): n_store 63) or
-        # the per-ray view encodings
-        b_t = (h_tiled and X is not enc and X is not venc) or (X is enc and enc_t)
-        n_store = 0
-        if X is enc and enc_t:
-            ldx, n_store, n_in = enc.shape[1], n_in, enc.shape[1]
-        # f16x3, the 256 x 256 / 128 x 256 / 256 x 64 products of the fused kernels' tiled
-        # tensors: one accumulator (aon_gemm f16_single) with dY at the chain's scale and X at
-        # the forward's 2^3, the scales both kernels range-guard their own splits at (pos_enc(x)
-        # and x itself: far inside the range)
-        single = (not bf16 and a_t and b_t
-                  and (n_out, n_in) in ((256, 256), (128, 256), (256, 64)))
-        gemm(dW[:, col0:] if col0 else dW, dY, X, n_out, n_in, R, lda=ldy, a_kc=False, ldb=ldx,
-             b_kc=False, b_rdiv=rdiv, ldc=dW.shape[1], a_scale=1.0,
-             b_scale=1.0 if bf16 else (8.0 if single else acts), rowsum=db,
-             a_amax=None if bf16 else work, mma_bf16=bf16, a_tiled=a_t, b_tiled=b_t,
-             n_store=n_store, f16_single=single)
+    dweight = functools.partial(level.dweight, G, R, bf16, work)
 
     # bf16: the eight 256 x 256 products (bottleneck, pts_linears.1-7) run as one aon_gemm_batch
     touched = [dzv, dzb, dz, draw, work, enc, venc, bot, hv, *h, *(t for wb in G for t in wb)]
     with _on_side(token, dev, touched), batched(cfg.batch_dweights, cfg.batch_128):
-        dweight(G[11][0], draw, 4, 3, hv, 128, 128, db=G[11][1], a_t=False)    # rgb_layer
-        dweight(G[10][0], dzv, 128, 128, bot, 256, 256, db=G[10][1])           # views_linear.0
-        dweight(G[10][0], dzv, 128, 128, venc, 27, 27, rdiv=S, col0=256)
-        dweight(G[9][0], dzb, 256, 256, h[7], 256, 256, db=G[9][1])            # bottleneck
-        dweight(G[8][0], draw[:, 3:], 4, 1, h[7], 256, 256, db=G[8][1], a_t=False)  # density
-        for i in range(7, -1, -1):                                             # pts_linears.i
+        dweight(11, d_raw, x_hv)                                  # rgb_layer
+        dweight(10, d_zv, x_bot)                                  # views_linear.0
+        dweight(10, d_zv, x_venc, col0=256, rdiv=S, bias=False)
+        dweight(9, d_zb, x_h[7])                                  # bottleneck
+        dweight(8, d_sigma, x_h[7])                               # density
+        for i in range(7, 0, -1):                                 # pts_linears.i
+            dweight(i, d_z[i], x_h[i - 1])
             if i == 5:
-                dweight(G[5][0], dz[5], 256, 256, h[4], 256, 256, db=G[5][1])
-                dweight(G[5][0], dz[5], 256, 256, enc, 63, 63, col0=256)
-            elif i == 0:
-                dweight(G[0][0], dz[0], 256, 256, enc, 63, 63, db=G[0][1])
-            else:
-                dweight(G[i][0], dz[i], 256, 256, h[i - 1], 256, 256, db=G[i][1])
-    _rec(timers, f"dweight{S}", e0, R)
+                dweight(5, d_z[5], x_enc, col0=256, bias=False)
+        dweight(0, d_z[0], x_enc)
+    level.record(timers, ev, f"dweight{S}", R)
 
 
 def _forward_level_fused(P, rays_o, rays_d, viewdirs, t_vals, raw, noise=None, masks=None,
@@ -435,20 +377,15 @@ class RenderLevel(torch.autograd.Function):
         if cfg.fused_forward:
             noise = L.contig(noise) if noise is not None else None
             masks = torch.empty((9, tiles.rows(R), 8), dtype=torch.int32, device=dev)
-            e0 = _ev(timers)
+            ev = level.events(timers)
             h, bot, hv = _forward_level_fused(P, L.contig(rays_o), L.contig(rays_d),
                                               L.contig(viewdirs), L.contig(t_vals), raw, noise,
                                               masks, bf16=bf16, enc=enc if bf16 else None)
-            _rec(timers, f"fwd_train{S}", e0, R)
+            level.record(timers, ev, f"fwd_train{S}", R)
         else:
             h, bot, hv = _forward_level(P, enc, venc, S, raw, noise)
-        comp = torch.empty((B, 3), device=dev)
-        acc = torch.empty((B,), device=dev)
-        weights = torch.empty((B, S), device=dev)
-        depth = torch.empty((B,), device=dev)
-        L.call("aon_composite_fwd", L.ptr(raw), 4, L.ptr(raw[:, 3:]), 4, L.ptr(t_vals),
-               L.ptr(rays_d), B, S, int(bool(white_bkgd)), L.ACT_VANILLA, L.ptr(comp), L.ptr(acc),
-               L.ptr(weights), L.ptr(depth), L.stream(dev))
+        comp, acc, depth, weights = level.composite_fwd(raw, t_vals, rays_d, white_bkgd,
+                                                        L.ACT_VANILLA)
         ctx.save_for_backward(rays_d, t_vals, enc, venc, raw, bot, hv, *h, *params)
         ctx.masks = masks
         ctx.h_tiled = cfg.fused_forward  # the fused forward keeps its tensors tiled
@@ -465,15 +402,9 @@ class RenderLevel(torch.autograd.Function):
         rays_d, t_vals, enc, venc, raw, bot, hv = saved[:7]
         h = list(saved[7:15])
         params = saved[15:]
-        dev = raw.device
         R = B * S
-        draw = torch.empty((R, 4), device=dev)
-        g_rgb = L.contig(g_rgb) if g_rgb is not None else torch.zeros((B, 3), device=dev)
-        L.call("aon_composite_bwd", L.ptr(raw), 4, L.ptr(raw[:, 3:]), 4, L.ptr(t_vals),
-               L.ptr(rays_d), B, S, int(white), L.ACT_VANILLA, L.ptr(g_rgb),
-               L.ptr(L.contig(g_acc)) if g_acc is not None else None,
-               L.ptr(L.contig(g_depth)) if g_depth is not None else None,
-               L.ptr(draw), L.ptr(draw[:, 3:]), 4, L.stream(dev))
+        draw = level.composite_bwd(raw, t_vals, rays_d, B, S, white, L.ACT_VANILLA, g_rgb, g_acc,
+                                   g_depth)
         P = [(params[2 * i], params[2 * i + 1]) for i in range(12)]
         G = [(torch.empty_like(w), torch.empty_like(b)) for w, b in P]
         cfg, timers = ctx.cfg, ctx.timers

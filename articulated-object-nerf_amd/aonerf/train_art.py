@@ -26,112 +26,32 @@ dL/dW_l = db l^T from the bias gradient db alone (aon_gemm with K = 1 / M = 1); 
 collects three such terms (deformation input, trunk input, skip), appearance one, articulation
 one, both levels add through autograd.  The regulariser 1e-4 * sum of mean code norms
 (:456-466) is aon_latent_reg.  All arithmetic is in HIP kernels; torch allocates, routes
-autograd and looks up / scatters the code-library rows (nn.Embedding).
+autograd and looks up / scatters the code-library rows (nn.Embedding).  The plumbing shared
+with train.py, the latent folds and the layer-by-layer walker (also the render's fallback,
+model_autodecoder.NeRFMLP._mlp) are level.py.
 """
+import functools
+
 import torch
 
 from . import _lib as L
-from . import tiles
-from . import train as _train
-from .linalg import ACT_SCALE, GRAD_SCALE, W_SCALE, batched, gemm, small_batched
+from . import level, tiles
+from .level import BOT, DEF0, DENS, DL, PTS0, RGB, VIEW0, art_layers  # noqa: F401 (layer order)
+from .level import Geo as _Geo
+from .linalg import batched, gemm, small_batched
 from .numerics import ART_FORWARD, DEFAULT
 from .train import (Adam, _amax_word, img2mse, learning_rate, loss_pair, masked_loss,  # noqa: F401 (shared)
                     mse2psnr, relu_masks)
 
-# parameter layout of one articulated NeRFMLP in ArtRenderLevel: 20 layers x (weight, bias)
-DEF0, DL, PTS0, DENS, BOT, VIEW0, RGB = 0, 4, 5, 13, 14, 15, 19
-
-
-def art_layers(mlp):
-    """The 20 nn.Linear layers of an articulated NeRFMLP in ArtRenderLevel order."""
-    return (list(mlp.deformations_linear) + [mlp.deformation_layer] + list(mlp.pts_linears)
-            + [mlp.density_layer, mlp.bottleneck_layer] + list(mlp.views_linear) + [mlp.rgb_layer])
-
-
-def _check_geometry(mlp):
-    ok = (mlp.netdepth == 8 and mlp.skip_layer == 4 and mlp.netdepth_deformation == 4
-          and mlp.netdepth_condition == 4 and mlp.input_ch == 3 and mlp.input_ch_view == 3
-          and mlp.num_rgb_channels == 3 and mlp.num_density_channels == 1)
-    if not ok:
-        raise ValueError("the articulated training path implements the reference's default layer "
-                         "counts (netdepth 8, skip 4, 4 deformation / 4 condition layers)")
-
-
-class _Geo:
-    """Widths of one articulated NeRFMLP (model_autodecoder.py:60-166)."""
-
-    def __init__(self, mlp):
-        _check_geometry(mlp)
-        self.wd, self.nw, self.wc = mlp.netwidth_deformation, mlp.netwidth, mlp.netwidth_condition
-        self.ne = mlp.pos_size_enc  # 3 + 6 (max_deg - min_deg)
-        self.min_deg, self.max_deg, self.deg_view = mlp.min_deg_point, mlp.max_deg_point, mlp.deg_view
-        self.nv = (mlp.deg_view * 2 + 1) * mlp.input_ch_view
-        self.n_shape, self.n_app = mlp.shape_latent_dim, mlp.appearance_latent_dim
-        self.n_art = mlp.articulation_latent_dim
-
-
-def _fold(W, b, c0, lat, exact=False):
-    """b + W[:, c0:c0+n] . lat (the latent columns of a layer as a per-call bias); exact (the
-    bf16 mode): on aon_gemm's exact-fp32 tiny-product path."""
-    N, n = W.shape[0], lat.shape[1]
-    out = torch.empty((1, N), device=W.device)
-    gemm(out, lat, W[:, c0:], 1, N, n, lda=n, a_kc=True, ldb=W.stride(0), b_kc=True, ldc=N,
-         bias=b, a_scale=1.0, b_scale=W_SCALE, exact_fp32=exact)
-    return out.reshape(-1)
-
-
-def _linear(out, X, ldx, W, bias, K, *, relu=False, X2=None, K2=0, ld2=0, rdiv2=1, ldo=None,
-            accumulate=False):
-    """out (R x N) (+)= [X | X2] W[:, :K+K2]^T + bias (+ReLU)."""
-    R, N = out.shape[0], W.shape[0]
-    gemm(out, X, W, R, N, K + K2, lda=ldx, a_kc=True, ldb=W.stride(0), b_kc=True,
-         ldc=ldo or out.stride(0), A2=X2, lda2=ld2, K1=K if X2 is not None else 0, a2_rdiv=rdiv2,
-         bias=bias, relu=relu, accumulate=accumulate, a_scale=ACT_SCALE, b_scale=W_SCALE)
-
 
 def _forward_level(geo, P, lat, xyz, venc, S, raw, noise=None, exact_folds=False):
-    """NeRFMLP.forward (model_autodecoder.py:168-239) layer by layer, keeping activations
-    (exact_folds: the latent folds on the exact-fp32 path, as the bf16 mode computes them)."""
-    R, dev = xyz.shape[0], xyz.device
-    shape, app, art = lat
-    wd, nw, wc, ne, nv = geo.wd, geo.nw, geo.wc, geo.ne, geo.nv
-    # deformation MLP on cat[xyz, shape, art] (:196-203), the latent columns folded
-    hd = torch.empty((4, R, wd), device=dev)
-    _linear(hd[0], xyz, 3, P[DEF0][0],
-            _fold(*P[DEF0], 3, torch.cat([shape, art], -1), exact_folds), 3, relu=True)
-    for i in range(1, 4):
-        _linear(hd[i], hd[i - 1], wd, *P[DEF0 + i], wd, relu=True)
-    delta = torch.empty((R, 3), device=dev)
-    _linear(delta, hd[3], wd, *P[DL], wd)  # deformation_layer (:205)
-    # x' = delta + xyz -> pos_enc (enc_after, :205-212); enc[:, :3] is x' itself
-    enc = torch.empty((R, ne), device=dev)
-    L.call("aon_cast_rays", L.ptr(xyz), None, None, R, 1, L.ptr(delta), 3, None, geo.min_deg,
-           geo.max_deg, L.ptr(enc), L.stream(dev))
-    # trunk on cat[enc, shape] with the skip concat cat[h4, enc, shape] (:214-220)
-    h = torch.empty((8, R, nw), device=dev)
-    W0 = P[PTS0][0]
-    _linear(h[0], enc, ne, W0, _fold(W0, P[PTS0][1], ne, shape, exact_folds), ne, relu=True)
-    for i in range(1, 8):
-        W_, b_ = P[PTS0 + i]
-        if i == 5:
-            _linear(h[5], h[4], nw, W_, _fold(W_, b_, nw + ne, shape, exact_folds), nw,
-                    relu=True, X2=enc, K2=ne, ld2=ne)
-        else:
-            _linear(h[i], h[i - 1], nw, W_, b_, nw, relu=True)
-    if noise is not None:  # raw_sigma + noise (:318-319), added in the GEMM epilogue
-        raw[:, 3].copy_(noise)
-    _linear(raw[:, 3:], h[7], nw, *P[DENS], nw, ldo=4, accumulate=noise is not None)
-    bot = torch.empty((R, nw), device=dev)
-    _linear(bot, h[7], nw, *P[BOT], nw)  # bottleneck, no activation (:225)
-    # view branch on cat[bottleneck, enc_dir tiled over samples, appearance] (:226-235)
-    hv = torch.empty((4, R, wc), device=dev)
-    Wv = P[VIEW0][0]
-    _linear(hv[0], bot, nw, Wv, _fold(Wv, P[VIEW0][1], nw + nv, app, exact_folds), nw,
-            relu=True, X2=venc, K2=nv, ld2=nv, rdiv2=S)
-    for i in range(1, 4):
-        _linear(hv[i], hv[i - 1], wc, *P[VIEW0 + i], wc, relu=True)
-    _linear(raw, hv[3], wc, *P[RGB], wc, ldo=4)  # rgb_layer (:237)
-    return hd, enc, h, bot, hv
+    """NeRFMLP.forward layer by layer (level.art_forward), keeping activations; each latent fold
+    runs just before its layer (exact_folds: exact fp32, as the bf16 mode computes them)."""
+    bufs = level.LayerBuffers(geo, xyz.shape[0], xyz.device, raw)
+    enc, _ = level.art_forward(
+        geo, P, lambda i: level.fold(*P[i], *level.fold_args(geo, lat, i), exact_folds), xyz, venc,
+        S, bufs, noise)
+    return bufs.t["hd"], enc, bufs.t["h"], bufs.t["bot"][0], bufs.t["hv"]
 
 
 # Which kernels, precision and (bf16 mode) forward numerics a level trains with is the MODEL's
@@ -149,30 +69,10 @@ def _forward_level(geo, P, lat, xyz, venc, S, raw, noise=None, exact_folds=False
 # step) and "bf16_trunk" (trunk, heads and view branch bf16: 0.987 -- the articulated gradients
 # are ill-conditioned in the forward values).
 
-_packed = {}
-
-
 def _params_struct(P, fb=None):
-    """AonMlpArtParams of one level's parameters (``fb``: folded biases by layer index)."""
-    fb = fb or {}
-    order = [DEF0 + i for i in range(4)] + [DL] + [PTS0 + i for i in range(8)] + [DENS, BOT] + \
-        [VIEW0 + i for i in range(4)] + [RGB]
-    # shape / dtype / device checked against the layer table (ValueError) before any pointer
-    # reaches a pack kernel; the C side checks the shapes again (aon_mlp_art_params, ABI 9)
-    return L.mlp_art_params([(P[i][0], fb.get(i, P[i][1])) for i in order])
-
-
-def _buffer(key, nbytes, dev, guard=False, params=()):
-    # one buffer per kind and device: a pack and the kernel reading it are stream-ordered.
-    # guard: a packed weight stream whose range-status word the next optimizer step over
-    # ``params`` (the packed parameters) checks
-    buf = _packed.get((key, str(dev)))
-    if buf is None:
-        buf = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=dev)
-        _packed[(key, str(dev))] = buf
-    if guard:
-        L.register_pack(("train_art", key), buf, params)
-    return buf
+    """AonMlpArtParams of one level's parameters (``fb``: folded biases by layer index), checked
+    against the layer table (ValueError) before any pointer reaches a pack kernel."""
+    return L.mlp_art_params(level.folded_pairs(P, fb or {}))
 
 
 def _pack(geo, P, lat, tag="", mixed=0, exact_folds=False):
@@ -182,15 +82,12 @@ def _pack(geo, P, lat, tag="", mixed=0, exact_folds=False):
     (aon_mlp_art_pack_mixed: 1 trunk bf16, 2 view branch bf16, 3 fp16 weights; range-guarded,
     their deformation part is fp16x3).  exact_folds (the bf16 mode): the folds on the exact-fp32
     path."""
-    shape, app, art = lat
-    dev = shape.device
+    dev = lat[0].device
     with small_batched():  # bf16: the four folds as one launch (exact-fp32 path, same bits)
-        fb = {DEF0: _fold(*P[DEF0], 3, torch.cat([shape, art], -1), exact_folds),
-              PTS0: _fold(*P[PTS0], geo.ne, shape, exact_folds),
-              PTS0 + 5: _fold(*P[PTS0 + 5], geo.nw + geo.ne, shape, exact_folds),
-              VIEW0: _fold(*P[VIEW0], geo.nw + geo.nv, app, exact_folds)}
-    buf = _buffer(f"fwd{'bf' if mixed else ''}{tag}", L.lib().aon_mlp_art_packed_bytes(), dev,
-                  guard=True, params=[t for wb in P for t in wb])
+        fb = level.folded_biases(geo, P, lat, exact_folds)
+    buf = level.buffer("train_art", f"fwd{'bf' if mixed else ''}{tag}",
+                       L.lib().aon_mlp_art_packed_bytes(), dev, guard=True,
+                       params=[t for wb in P for t in wb])
     if mixed:
         L.call("aon_mlp_art_pack_mixed", L.ctypes.byref(_params_struct(P, fb)), mixed, L.ptr(buf),
                L.stream(dev))
@@ -201,11 +98,8 @@ def _pack(geo, P, lat, tag="", mixed=0, exact_folds=False):
 
 def _pack_bwd(P, dev, tag="", bf16=False):
     """The transposed weight stream of the fused backward chain (aon_mlp_art_bwd_pack[_bf16])."""
-    buf = _buffer(f"bwd{'bf' if bf16 else ''}{tag}", L.lib().aon_mlp_art_bwd_packed_bytes(), dev,
-                  guard=not bf16, params=[t for wb in P for t in wb])
-    L.call("aon_mlp_art_bwd_pack_bf16" if bf16 else "aon_mlp_art_bwd_pack",
-           L.ctypes.byref(_params_struct(P)), L.ptr(buf), L.stream(dev))
-    return buf
+    return level.pack_bwd("train_art", "aon_mlp_art_bwd_pack",
+                          L.lib().aon_mlp_art_bwd_packed_bytes, _params_struct, P, dev, tag, bf16)
 
 
 def _forward_level_fused(geo, P, lat, rays_o, rays_d, viewdirs, t_vals, raw, noise=None,
@@ -240,7 +134,7 @@ def _forward_level_fused(geo, P, lat, rays_o, rays_d, viewdirs, t_vals, raw, noi
     # (f16_acts, 4, and f16x3, 0, read the plain fp16x3 stream)
     packed = _pack(geo, P, lat, S, mixed if mixed_stream else 0,
                    exact_folds=bf16 if exact_folds is None else exact_folds)
-    e0 = _train._ev(timers)
+    ev = level.events(timers)
     args = (L.ptr(packed), L.ptr(rays_o), L.ptr(rays_d), L.ptr(viewdirs), L.ptr(t_vals), B, S,
             L.ptr(noise) if noise is not None else None, L.ptr(hd), L.ptr(h), L.ptr(bot),
             L.ptr(hv), L.ptr(enc), L.ptr(xyz), L.ptr(raw), L.ptr(masks))
@@ -249,7 +143,7 @@ def _forward_level_fused(geo, P, lat, rays_o, rays_d, viewdirs, t_vals, raw, noi
     else:
         L.call("aon_mlp_art_fwd_train", *args, L.stream(dev))
     L.snapshot_pack(packed)  # the forward was the pack's last reader (range guard, _lib)
-    _train._rec(timers, f"art_fwd_train{S}", e0, R)
+    level.record(timers, ev, f"art_fwd_train{S}", R)
     return (xyz, hd, enc, h, bot, hv) + ((enc_bf,) if return_enc_bf else ())
 
 
@@ -278,12 +172,6 @@ def _enc_tiled(enc, width):
     return tiles.tile(pad)
 
 
-def _fused_ok(geo):
-    # the fused kernel is compiled for the default widths (mlp_layout.hpp kLayersArt)
-    return (geo.wd == 128 and geo.nw == 256 and geo.wc == 128 and geo.ne == 63 and geo.nv == 27
-            and geo.min_deg == 0)
-
-
 def _backward_level(geo, P, G, lat, dlat, xyz, enc, venc, S, hd, h, bot, hv, draw):
     """Autograd of _forward_level from dL/draw (R x 4): G[i] = (dW, db) of layer i; dlat =
     (dshape, dapp, dart) (1 x n each) receive the latent-code gradients.  Every dY enters the
@@ -294,37 +182,19 @@ def _backward_level(geo, P, G, lat, dlat, xyz, enc, venc, S, hd, h, bot, hv, dra
     enc = enc_rows(geo, enc, R)
     shape, app, art = lat
     dshape, dapp, dart = dlat
-    gs, acts = GRAD_SCALE, ACT_SCALE
     word = torch.zeros((1,), dtype=torch.int32, device=dev)  # stream-ordered: reused per call
 
-    def amax(dY):
-        return _amax_word(draw if dY.data_ptr() == draw.data_ptr() + 12 else dY, word)
+    def dweight(i, dY, ldy, X, ldx, n_in, col0=0, rdiv=1, bias=True, of=None):
+        # ``of``: the tensor whose max scales dY (default dY itself)
+        level.gemm_dweight(G[i][0], G[i][1] if bias else None, dY, ldy, X, ldx, n_in, R,
+                           col0=col0, rdiv=rdiv, amax=_amax_word(dY if of is None else of, word))
 
-    def dweight(i, dY, ldy, X, ldx, n_in, col0=0, rdiv=1, bias=True):
-        # dW_i[:, col0:col0+n_in] = dY^T X (K = rows, split-K); db_i = sum_rows dY, same pass
-        dW = G[i][0]
-        n_out = dW.shape[0]
-        gemm(dW[:, col0:] if col0 else dW, dY, X, n_out, n_in, R, lda=ldy, a_kc=False, ldb=ldx,
-             b_kc=False, b_rdiv=rdiv, ldc=dW.stride(0), a_scale=1.0, b_scale=acts,
-             rowsum=G[i][1] if bias else None, a_amax=amax(dY))
-
-    def dinput(dX, dY, ldy, i, col0, n_in, mask=None, accumulate=False):
-        # dX (R x n_in) (+)= dY W_i[:, col0:col0+n_in] (* relu'(mask))
-        W = P[i][0]
-        gemm(dX, dY, W[:, col0:] if col0 else W, R, n_in, W.shape[0], lda=ldy, a_kc=True,
-             ldb=W.stride(0), b_kc=False, ldc=dX.stride(0), mask=mask,
-             ldm=mask.stride(0) if mask is not None else 0, accumulate=accumulate, a_scale=1.0,
-             b_scale=W_SCALE, a_amax=amax(dY))
+    def dinput(dX, dY, ldy, i, col0, n_in, mask=None, accumulate=False, of=None):
+        level.gemm_dinput(dX, dY, ldy, P[i][0], n_in, R, col0=col0, mask=mask,
+                          accumulate=accumulate, amax=_amax_word(dY if of is None else of, word))
 
     def dlatent(i, col0, l, dl, accumulate):
-        # z = W [x; l] + b with l on every row: dW[:, col0:col0+n] = db l^T, dl (+)= db^T W_l
-        dW, db = G[i]
-        W = P[i][0]
-        n_out, n = W.shape[0], l.shape[1]
-        gemm(dW[:, col0:], db, l, n_out, n, 1, lda=1, a_kc=True, ldb=n, b_kc=False,
-             ldc=dW.stride(0), a_scale=gs, b_scale=1.0)
-        gemm(dl, db, W[:, col0:], 1, n, n_out, lda=n_out, a_kc=True, ldb=W.stride(0), b_kc=False,
-             ldc=n, accumulate=accumulate, a_scale=gs, b_scale=W_SCALE)
+        level.dlatent(*G[i], P[i][0], col0, l, dl, accumulate)
 
     # rgb head and the view branch
     dweight(RGB, draw, 4, hv[3], wc, wc)
@@ -343,10 +213,10 @@ def _backward_level(geo, P, G, lat, dlat, xyz, enc, venc, S, hd, h, bot, hv, dra
     del dz, dz2
     # bottleneck + density heads on h7
     dweight(BOT, dbot, nw, h[7], nw, nw)
-    dweight(DENS, draw[:, 3:], 4, h[7], nw, nw)
+    dweight(DENS, draw[:, 3:], 4, h[7], nw, nw, of=draw)  # the sigma column at d raw's scale
     dy = torch.empty((R, nw), device=dev)
     dinput(dy, dbot, nw, BOT, 0, nw)
-    dinput(dy, draw[:, 3:], 4, DENS, 0, nw, mask=h[7], accumulate=True)
+    dinput(dy, draw[:, 3:], 4, DENS, 0, nw, mask=h[7], accumulate=True, of=draw)
     del dbot
     # trunk; the gradient w.r.t. enc = pos_enc(x') collects the skip and the first layer
     denc = torch.empty((R, ne), device=dev)
@@ -412,83 +282,66 @@ def _backward_level_fused(geo, P, G, lat, dlat, xyz, enc, venc, S, hd, h, bot, h
     dz = torch.empty((8, NR, nw), device=dev, dtype=dt)
     dxp = torch.empty((R, 3), device=dev)
     dzd = torch.empty((4, NR, wd), device=dev, dtype=dt)
-    work = _buffer("work", 4, dev)
+    work = level.buffer("train_art", "work", 4, dev)
     packed = _pack_bwd(P, dev, S, bf16)
     enc_t = enc.shape[1] != ne  # the fused forward's tiled copy
     enc_chain = enc if enc_t else _enc_tiled(enc, 16 if bf16 else 64)
-    e0 = _train._ev(timers)
-    L.call("aon_mlp_art_bwd_bf16" if bf16 else "aon_mlp_art_bwd", L.ptr(packed), L.ptr(draw), L.ptr(masks), L.ptr(enc_chain), R,
-           L.ptr(dzv), L.ptr(dbot), L.ptr(dz), L.ptr(dxp), L.ptr(dzd), L.ptr(work), L.stream(dev))
+    ev = level.events(timers)
+    L.call("aon_mlp_art_bwd_bf16" if bf16 else "aon_mlp_art_bwd", L.ptr(packed), L.ptr(draw),
+           L.ptr(masks), L.ptr(enc_chain), R, L.ptr(dzv), L.ptr(dbot), L.ptr(dz), L.ptr(dxp),
+           L.ptr(dzd), L.ptr(work), L.stream(dev))
     L.snapshot_pack(packed)  # the chain was the pack's last reader
-    _train._rec(timers, f"art_bwd_chain{S}", e0, R)
-    e0 = _train._ev(timers)
-    gs, acts = GRAD_SCALE, ACT_SCALE
+    level.record(timers, ev, f"art_bwd_chain{S}", R)
+    ev = level.events(timers)
 
-    def dweight(i, dY, ldy, X, ldx, n_in, col0=0, rdiv=1, bias=True, chain_scale=True, a_t=True):
-        n_store = 0
-        if X is enc and bf16 and enc_bf is not None:  # the tiled bf16 copy, 63 of 128 columns
-            X, ldx, n_store, n_in = enc_bf, 128, n_in, 128
-        elif X is enc and enc_t:  # the fused fp16x3 forward's tiled fp32 copy, 63 of 64 columns
-            if enc.shape[1] != 64:
-                raise ValueError("the bf16 forward keeps 16 enc columns: pass its enc_bf")
-            ldx, n_store, n_in = 64, n_in, 64
-        # chain_scale: dY is in the chain's d raw domain (draw, view/trunk outputs): A rides at
-        # the chain's own per-call scale from max |d raw| (the word it left in `work`); the
-        # deformation branch (dL/dx' carries pos_enc's 2^9, rescaled per sample) keeps 2^10.
-        # a_t: dY is one of the chain's tiled gradients; X is tiled when it is a kept activation.
-        # bf16: one bf16 MFMA per product, no scales (bf16 has fp32's exponent range)
-        dW = G[i][0]
-        b_t = ((h_tiled and X is not enc and X is not venc and X is not xyz) or X is enc_bf
-               or (X is enc and enc_t))
-        # f16x3, the 256 x 256 / 128 x 256 / 256 x 64 products of the fused kernels' tiled
-        # tensors: one accumulator (aon_gemm f16_single), dY at the chain's scale, X at the
-        # forward's 2^3 (train.py; pos_enc(x') and x' far inside the range)
-        single = (not bf16 and chain_scale and a_t and b_t and ldx == n_in
-                  and (dW.shape[0], n_in) in ((256, 256), (128, 256), (256, 64)))
-        gemm(dW[:, col0:] if col0 else dW, dY, X, dW.shape[0], n_in, R, lda=ldy, a_kc=False,
-             ldb=ldx, b_kc=False, b_rdiv=rdiv, ldc=dW.stride(0),
-             a_scale=1.0 if (chain_scale or bf16) else gs,
-             b_scale=1.0 if bf16 else (8.0 if single else acts),
-             rowsum=G[i][1] if bias else None,
-             a_amax=work if (chain_scale and not bf16) else None, mma_bf16=bf16, a_tiled=a_t,
-             b_tiled=b_t, n_store=n_store, f16_single=single)
+    # the operands (level.Operand): d raw and dL/dx' row-major, the chain's gradients tiled (the
+    # deformation branch's at the fixed 2^10), the kept activations tiled after the fused forward
+    (d_raw, d_sigma), d_xp = level.draw_operands(draw), level.Operand(dxp, 3, False, level.DXP)
+    d_bot, *d_z = level.operands((dbot, *dz.unbind(0)), nw, True, level.CHAIN)
+    d_zv = level.operands(dzv.unbind(0), wc, True, level.CHAIN)
+    d_zd = level.operands(dzd.unbind(0), wd, True, level.CHAIN_DEF)
+    x_hd, x_hv = level.operands(hd, wd, h_tiled, level.ACT), level.operands(hv, wc, h_tiled, level.ACT)
+    x_bot, *x_h = level.operands((bot, *h), nw, h_tiled, level.ACT)
+    if bf16 and enc_bf is not None:
+        x_enc = level.enc_operand(enc_bf)
+    elif enc_t and enc.shape[1] != 64:
+        raise ValueError("the bf16 forward keeps 16 enc columns: pass its enc_bf")
+    else:
+        x_enc = level.enc_operand(enc)
+    x_venc, x_xyz = level.Operand(venc, nv, False, level.VENC), level.Operand(xyz, 3, False, level.XYZ)
+
+    dweight = functools.partial(level.dweight, G, R, bf16, work)
 
     def dlatent(i, col0, l, dl, accumulate):
         # (bf16 mode: the exact-fp32 tiny-product path)
-        dW, db = G[i]
-        W = P[i][0]
-        n_out, n = W.shape[0], l.shape[1]
-        gemm(dW[:, col0:], db, l, n_out, n, 1, lda=1, a_kc=True, ldb=n, b_kc=False,
-             ldc=dW.stride(0), a_scale=gs, b_scale=1.0, exact_fp32=bf16)
-        gemm(dl, db, W[:, col0:], 1, n, n_out, lda=n_out, a_kc=True, ldb=W.stride(0), b_kc=False,
-             ldc=n, accumulate=accumulate, a_scale=gs, b_scale=W_SCALE, exact_fp32=bf16)
+        level.dlatent(*G[i], P[i][0], col0, l, dl, accumulate, exact=bf16)
 
     # every whole-tile product of the level deferred to aon_gemm_batch launches (bf16: the eight
     # 256 x 256 ones -- bottleneck, pts_linears.1-7 -- and the 128-wide view / deformation / enc
     # column ones; fp16x3: all as the fp16x3 class), flushed before the latent terms read the
     # bias gradients; the latent terms then run in the same order as before (bit-identical)
     with batched(cfg.batch_dweights, cfg.batch_128):
-        dweight(RGB, draw, 4, hv[3], wc, wc, a_t=False)                   # rgb_layer
+        dweight(RGB, d_raw, x_hv[3])                                      # rgb_layer
         for i in range(3, 0, -1):                                         # views_linear.i
-            dweight(VIEW0 + i, dzv[i], wc, hv[i - 1], wc, wc)
-        dweight(VIEW0, dzv[0], wc, bot, nw, nw)                           # views_linear.0
-        dweight(VIEW0, dzv[0], wc, venc, nv, nv, col0=nw, rdiv=S, bias=False)
-        dweight(BOT, dbot, nw, h[7], nw, nw)                              # bottleneck
-        dweight(DENS, draw[:, 3:], 4, h[7], nw, nw, a_t=False)            # density
+            dweight(VIEW0 + i, d_zv[i], x_hv[i - 1])
+        dweight(VIEW0, d_zv[0], x_bot)                                    # views_linear.0
+        dweight(VIEW0, d_zv[0], x_venc, col0=nw, rdiv=S, bias=False)
+        dweight(BOT, d_bot, x_h[7])                                       # bottleneck
+        dweight(DENS, d_sigma, x_h[7])                                    # density
         for i in range(7, 0, -1):                                         # pts_linears.i
-            dweight(PTS0 + i, dz[i], nw, h[i - 1], nw, nw)
-        dweight(PTS0 + 5, dz[5], nw, enc, ne, ne, col0=nw, bias=False)
-        dweight(PTS0, dz[0], nw, enc, ne, ne)                             # pts_linears.0
-        dweight(DL, dxp, 3, hd[3], wd, wd, chain_scale=False, a_t=False)  # deformation_layer
+            dweight(PTS0 + i, d_z[i], x_h[i - 1])
+        dweight(PTS0 + 5, d_z[5], x_enc, col0=nw, bias=False)
+        dweight(PTS0, d_z[0], x_enc)                                      # pts_linears.0
+        dweight(DL, d_xp, x_hd[3])                                        # deformation_layer
         for i in range(3, 0, -1):                                         # deformations_linear.i
-            dweight(DEF0 + i, dzd[i], wd, hd[i - 1], wd, wd, chain_scale=False)
+            dweight(DEF0 + i, d_zd[i], x_hd[i - 1])
         if bf16:  # deformations_linear.0's xyz columns: (xyz^T dZ)^T on the skinny kernel, the
             # bias gradient as dZ's column sums (a 128-wide tile for 3 columns took 0.12 ms)
             gemm(G[DEF0][0], xyz, dzd[0], 3, wd, R, lda=3, a_kc=False, ldb=wd, b_kc=False,
                  ldc=G[DEF0][0].stride(0), rowsum=G[DEF0][1], mma_bf16=True, b_tiled=True,
                  c_trans=True)
         else:
-            dweight(DEF0, dzd[0], wd, xyz, 3, 3, chain_scale=False)       # deformations_linear.0
+            dweight(DEF0, d_zd[0], x_xyz)                                 # deformations_linear.0
     # the latent terms read the bias gradients just flushed; bf16 (exact-fp32 tiny products): all
     # ten as ONE aon_gemm_small_batch launch, bit-identical to ten launches in this order
     with small_batched():
@@ -497,7 +350,7 @@ def _backward_level_fused(geo, P, G, lat, dlat, xyz, enc, venc, S, hd, h, bot, h
         dlatent(PTS0, ne, shape, dshape, True)
         dlatent(DEF0, 3, shape, dshape, True)
         dlatent(DEF0, 3 + geo.n_shape, art, dart, False)
-    _train._rec(timers, f"art_dweight{S}", e0, R)
+    level.record(timers, ev, f"art_dweight{S}", R)
 
 
 class ArtRenderLevel(torch.autograd.Function):
@@ -527,7 +380,7 @@ class ArtRenderLevel(torch.autograd.Function):
         noise = L.contig(noise) if noise is not None else None
         masks = None  # ReLU' bits for the fused backward chain (built there when None)
         enc_bf = None  # the bf16 forward's tiled pos_enc(x') copy
-        if cfg.fused_forward and _fused_ok(geo):
+        if cfg.fused_forward and geo.fused_ok:
             masks = torch.empty((16, tiles.rows(R), 8), dtype=torch.int32, device=dev)
             xyz, hd, enc, h, bot, hv, enc_bf = _forward_level_fused(
                 geo, P, lat, L.contig(rays_o), L.contig(rays_d), L.contig(viewdirs),
@@ -539,13 +392,8 @@ class ArtRenderLevel(torch.autograd.Function):
                    L.ptr(xyz), 0, 0, None, L.stream(dev))
             hd, enc, h, bot, hv = _forward_level(geo, P, lat, xyz, venc, S, raw, noise,
                                                  exact_folds=cfg.bf16)
-        comp = torch.empty((B, 3), device=dev)
-        acc = torch.empty((B,), device=dev)
-        weights = torch.empty((B, S), device=dev)
-        depth = torch.empty((B,), device=dev)
-        L.call("aon_composite_fwd", L.ptr(raw), 4, L.ptr(raw[:, 3:]), 4, L.ptr(t_vals),
-               L.ptr(rays_d), B, S, int(bool(white_bkgd)), L.ACT_ARTIC, L.ptr(comp), L.ptr(acc),
-               L.ptr(weights), L.ptr(depth), L.stream(dev))
+        comp, acc, depth, weights = level.composite_fwd(raw, t_vals, rays_d, white_bkgd,
+                                                        L.ACT_ARTIC)
         ctx.save_for_backward(rays_d, t_vals, xyz, enc, venc, raw, hd, h, bot, hv, *lat, *params)
         ctx.masks = masks
         ctx.enc_bf = enc_bf if masks is not None else None
@@ -564,20 +412,13 @@ class ArtRenderLevel(torch.autograd.Function):
         rays_d, t_vals, xyz, enc, venc, raw, hd, h, bot, hv = saved[:10]
         lat = saved[10:13]
         params = saved[13:]
-        dev = raw.device
         R = B * S
-        draw = torch.empty((R, 4), device=dev)
-        if g_rgb is None:
-            g_rgb = torch.zeros((B, 3), device=dev)
-        L.call("aon_composite_bwd", L.ptr(raw), 4, L.ptr(raw[:, 3:]), 4, L.ptr(t_vals),
-               L.ptr(rays_d), B, S, int(white), L.ACT_ARTIC, L.ptr(L.contig(g_rgb)),
-               L.ptr(L.contig(g_acc)) if g_acc is not None else None,
-               L.ptr(L.contig(g_depth)) if g_depth is not None else None,
-               L.ptr(draw), L.ptr(draw[:, 3:]), 4, L.stream(dev))
+        draw = level.composite_bwd(raw, t_vals, rays_d, B, S, white, L.ACT_ARTIC, g_rgb, g_acc,
+                                   g_depth)
         P = [(params[2 * i], params[2 * i + 1]) for i in range(20)]
         G = [(torch.empty_like(w), torch.empty_like(b)) for w, b in P]
         dlat = tuple(torch.empty_like(x) for x in lat)
-        if ctx.cfg.fused_backward and _fused_ok(geo):
+        if ctx.cfg.fused_backward and geo.fused_ok:
             _backward_level_fused(geo, P, G, lat, dlat, xyz, enc, venc, S, hd, h, bot, hv, draw,
                                   ctx.masks, ctx.h_tiled, ctx.enc_bf, timers=ctx.timers,
                                   cfg=ctx.cfg)
@@ -596,9 +437,10 @@ def render_level(mlp, rays_o, rays_d, viewdirs, t_vals, white_bkgd, latents, noi
     """One NeRF_AE_Art level under autograd -> (comp_rgb, acc, depth, weights); ``cfg``: the
     model's TrainNumerics."""
     params = [p for m in art_layers(mlp) for p in (m.weight, m.bias)]
-    geo = getattr(mlp, "_geo", None)
-    if geo is None:
-        geo = mlp._geo = _Geo(mlp)
+    geo = level.geo_of(mlp)
+    if not geo.default_depths:
+        raise ValueError("the articulated training path implements the reference's default layer "
+                         "counts (netdepth 8, skip 4, 4 deformation / 4 condition layers)")
     return ArtRenderLevel.apply(geo, cfg, timers, rays_o, rays_d, viewdirs, t_vals,
                                 bool(white_bkgd), noise,
                                 latents["density"], latents["color"], latents["articulation"],

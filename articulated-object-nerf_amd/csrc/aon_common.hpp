@@ -17,13 +17,15 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 // thread-local error message behind aon_last_error()
 void set_error(const std::string& msg);
 
-#define AON_REQUIRE(cond, msg)                                   \
+// (fn: the name the message carries -- a shared check reports as the function that called it)
+#define AON_REQUIRE_AS(fn, cond, msg)                            \
   do {                                                           \
     if (!(cond)) {                                               \
-      ::aon::set_error(std::string(__func__) + ": " + (msg));    \
+      ::aon::set_error(std::string(fn) + ": " + (msg));          \
       return -1;                                                 \
     }                                                            \
   } while (0)
+#define AON_REQUIRE(cond, msg) AON_REQUIRE_AS(__func__, cond, msg)
 
 inline int launch_status(const char* fn) {
   hipError_t e = hipGetLastError();

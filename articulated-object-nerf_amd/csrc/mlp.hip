@@ -314,37 +314,43 @@ extern "C" int aon_mlp_pack(const aon_mlp_params* prm, int precision, void* pack
   return launch_status(__func__);
 }
 
+// the precisions a render entry point refuses, reported as fn (fp32_ok: not a two-pass entry)
+static int check_render_precision(const char* fn, int precision, bool fp32_ok) {
+  AON_REQUIRE_AS(fn, precision != AON_PREC_F16X3_TRAIN,
+                 "AON_PREC_F16X3_TRAIN is the training forward's stream (aon_mlp_fwd_train): "
+                 "render with an AON_PREC_F16X3 pack");
+  AON_REQUIRE_AS(fn, fp32_ok || precision != AON_PREC_FP32,
+                 "AON_PREC_FP32 has no two-pass kernels: render a fp32 pack with aon_mlp_fwd");
+  AON_REQUIRE_AS(fn, precision == AON_PREC_F16X3 || precision == AON_PREC_FP32,
+                 "unsupported precision (AON_PREC_BF16 is the training forward's: "
+                 "aon_mlp_fwd_train_bf16)");
+  return 0;
+}
+
+// mode: the kernels' MODE (0: rays + t, 1: encoded inputs)
 static int mlp_launch(int mode, const void* packed, int precision, const float* a0,
                       const float* a1, const float* a2, const float* a3, int64_t B, int S,
                       int act, float* raw, aon_stream_t stream) {
   AON_REQUIRE(packed && raw && a0 && a1, "null pointer");
-  AON_REQUIRE(precision != AON_PREC_F16X3_TRAIN,
-              "AON_PREC_F16X3_TRAIN is the training forward's stream (aon_mlp_fwd_train): render "
-              "with an AON_PREC_F16X3 pack");
-  AON_REQUIRE(precision == AON_PREC_FP32 || precision == AON_PREC_F16X3,
-              "unsupported precision (AON_PREC_BF16 is the training forward's: aon_mlp_fwd_train_bf16)");
-  AON_REQUIRE(B >= 0 && S >= 1, "bad shape");
-  AON_REQUIRE(act >= AON_ACT_NONE && act <= AON_ACT_ARTIC, "bad activation");
-  AON_REQUIRE(aligned16(packed) && aligned16(raw), "packed / raw must be 16-byte aligned");
+  if (check_render_precision(__func__, precision, true)) return -1;
+  if (check_fwd_args(__func__, packed, raw, B, S, act)) return -1;
   const int64_t N = B * S;
   if (N == 0) return 0;
-  AON_REQUIRE((N + kRowsPerBlock - 1) / kRowsPerBlock < (1ll << 31), "too many rows");
+  AON_REQUIRE(rows_ok(N), "too many rows");
 #if AON_DATAFLOW_WS_BUILD
   if (precision == AON_PREC_F16X3 && mode == 0)
     return launch_ws_f16x3(packed, a0, a1, a2, a3, B, S, act, raw, (hipStream_t)stream);
 #endif
   if (precision == AON_PREC_F16X3)
-    return launch_f16x3(mode, AON_F16X3_NCOL, packed, a0, a1, a2, a3, B, S, act, raw,
-                        (hipStream_t)stream);
-  const int grid = static_cast<int>((N + kRowsPerBlock - 1) / kRowsPerBlock);
+    return launch_f16x3_render(mode == 1, AON_F16X3_NCOL, packed, a0, a1, a2, a3, B, S, act, raw,
+                               (hipStream_t)stream);
+  static_assert(kRowsPerBlock == GeomH<1>::kRowsPerBlock, "the fp32 grid is GeomH<1>'s (rows_ok)");
+  const unsigned grid = chain_grid<GeomH<1>>(N);
   const f4* ws = static_cast<const f4*>(packed);
-  const float* bias = reinterpret_cast<const float*>(static_cast<const char*>(packed) + kStreamBytesF32);
-  if (mode == 0)
-    hipLaunchKernelGGL(k_mlp_fwd_f32<0>, grid, kThreads, 0, (hipStream_t)stream, ws, bias, a0, a1,
-                       a2, a3, B, S, act, raw);
-  else
-    hipLaunchKernelGGL(k_mlp_fwd_f32<1>, grid, kThreads, 0, (hipStream_t)stream, ws, bias, a0, a1,
-                       a2, a3, B, S, act, raw);
+  static_assert(NetVanillaH::kStreamBytes == kStreamBytesF32, "fp32 and fp16x3 share the block grid");
+  const float* bias = stream_bias<NetVanillaH>(packed);
+  hipLaunchKernelGGL(mode == 0 ? k_mlp_fwd_f32<0> : k_mlp_fwd_f32<1>, grid, kThreads, 0,
+                     (hipStream_t)stream, ws, bias, a0, a1, a2, a3, B, S, act, raw);
   return launch_status("aon_mlp_fwd");
 }
 
@@ -366,18 +372,10 @@ static int two_pass_check(const void* packed, int precision, const float* rays_o
                           const float* rays_d, const float* t, int64_t B, int S, int act,
                           const float* raw) {
   AON_REQUIRE(packed && raw && rays_o && rays_d && t, "null pointer");
-  AON_REQUIRE(precision != AON_PREC_F16X3_TRAIN,
-              "AON_PREC_F16X3_TRAIN is the training forward's stream (aon_mlp_fwd_train): render "
-              "with an AON_PREC_F16X3 pack");
-  AON_REQUIRE(precision != AON_PREC_FP32,
-              "AON_PREC_FP32 has no two-pass kernels: render a fp32 pack with aon_mlp_fwd");
-  AON_REQUIRE(precision == AON_PREC_F16X3,
-              "unsupported precision (AON_PREC_BF16 is the training forward's: aon_mlp_fwd_train_bf16)");
-  AON_REQUIRE(B >= 0 && S >= 1, "bad shape");
-  AON_REQUIRE(act >= AON_ACT_NONE && act <= AON_ACT_ARTIC, "bad activation");
-  AON_REQUIRE(aligned16(packed) && aligned16(raw), "packed / raw must be 16-byte aligned");
+  if (check_render_precision(__func__, precision, false)) return -1;
+  if (check_fwd_args(__func__, packed, raw, B, S, act)) return -1;
   if (B * S == 0) return 1;
-  AON_REQUIRE((B * S + 127) / 128 < (1ll << 31), "too many rows");
+  AON_REQUIRE(rows_ok(B * S), "too many rows");
   return 0;
 }
 
@@ -410,10 +408,10 @@ extern "C" int aon_mlp_fwd_train(const void* packed, const float* rays_o, const 
               "packed / output buffers must be 16-byte aligned");
   const int64_t N = B * S;
   if (N == 0) return 0;
-  AON_REQUIRE((N + 127) / 128 < (1ll << 31), "too many rows");
+  AON_REQUIRE(rows_ok(N), "too many rows");
   const TrainStore ts{h, bot, hv, noise, reinterpret_cast<uint2*>(masks)};
-  return launch_f16x3(2, 1, packed, rays_o, rays_d, viewdirs, t, B, S, AON_ACT_NONE, raw,
-                      (hipStream_t)stream, &ts);
+  return launch_f16x3_train(false, ts, packed, rays_o, rays_d, viewdirs, t, B, S, raw,
+                            (hipStream_t)stream);
 }
 
 extern "C" int aon_mlp_fwd_train_bf16(const void* packed, const float* rays_o,
@@ -429,10 +427,10 @@ extern "C" int aon_mlp_fwd_train_bf16(const void* packed, const float* rays_o,
               "packed / output buffers must be 16-byte aligned");
   const int64_t N = B * S;
   if (N == 0) return 0;
-  AON_REQUIRE((N + 127) / 128 < (1ll << 31), "too many rows");
+  AON_REQUIRE(rows_ok(N), "too many rows");
   const TrainStore ts{reinterpret_cast<float*>(h), reinterpret_cast<float*>(bot),
                       reinterpret_cast<float*>(hv), noise, reinterpret_cast<uint2*>(masks),
                       reinterpret_cast<__bf16*>(enc)};
-  return launch_f16x3(3, 1, packed, rays_o, rays_d, viewdirs, t, B, S, AON_ACT_NONE, raw,
-                      (hipStream_t)stream, &ts);
+  return launch_f16x3_train(true, ts, packed, rays_o, rays_d, viewdirs, t, B, S, raw,
+                            (hipStream_t)stream);
 }

@@ -48,11 +48,10 @@ __global__ __launch_bounds__(GeomH<NCOL>::kThreads, NCOL == 1 ? 2 : 1) void k_ml
   constexpr bool BFV = PREC == 3;  // bf16 view branch (venc and the bottleneck's output in bf16)
   constexpr bool F16W = PREC == 4;  // fp16 weights past the deformation MLP
   constexpr int X1F = PREC == 5 ? kArtMix.hi : -1;  // fp16 activations past it
-  constexpr int kStash = G::kWaves * 64 * 6 * NCOL;  // f4: enc 2 k-steps + venc 1, hi & lo
-  __shared__ f4 smem[kLdsWeights + Net::kBiasFloats / 4 + kStash];
-  float* bias_s = reinterpret_cast<float*>(smem + kLdsWeights);
-  f4* stash = smem + kLdsWeights + Net::kBiasFloats / 4 + (threadIdx.x >> 6) * 64 * 6 * NCOL +
-              (threadIdx.x & 63);  // lane-private slots
+  using Lds = ChainLds<Net, G, 6 * NCOL>;  // per lane: enc 2 k-steps + venc 1, hi & lo
+  __shared__ f4 smem[Lds::kF4];
+  float* bias_s = Lds::bias(smem);
+  f4* stash = Lds::stash(smem);
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, j = lane & 15;
@@ -65,12 +64,7 @@ __global__ __launch_bounds__(GeomH<NCOL>::kThreads, NCOL == 1 ? 2 : 1) void k_ml
           WeightPipe<Net, G::kThreads>>::type>::type;
   using T = typename std::conditional<PREC != 0, __bf16, float>::type;
   WP p;
-  p.wbuf = smem;
-  p.src = wstream;
-  p.tid = tid;
-  p.lane = lane;
-  p.start();
-  for (int i = tid; i < Net::kBiasFloats; i += G::kThreads) bias_s[i] = bias_g[i];
+  start_chain<Net, G::kThreads>(p, smem, wstream, tid, lane, bias_s, bias_g);
 
   // deformation input (xyz, natural order: lane group 0 elements 0..2) and enc_dir fragments
   Frag<1, NCOL> din, venc;
@@ -262,19 +256,13 @@ static int art_pack(const aon_mlp_art_params* prm, void* packed, aon_stream_t st
   a.w[A_DEN] = prm->density_w;      a.b[A_DEN] = prm->density_b;
   a.w[A_BOT] = prm->bottleneck_w;   a.b[A_BOT] = prm->bottleneck_b;
   a.w[A_RGB] = prm->rgb_w;          a.b[A_RGB] = prm->rgb_b;
-  for (int i = 0; i < kNumLayersArt; ++i) {
-    AON_REQUIRE(a.w[i] && a.b[i], "null layer parameter");
-    a.layers[i] = kLayersArt[i];
-    a.ldw[i] = kLayersArt[i].len_a + kLayersArt[i].len_b;
-  }
+  for (int i = 0; i < kNumLayersArt; ++i) AON_REQUIRE(a.w[i] && a.b[i], "null layer parameter");
+  fill_net<NetArtH>(a);
   // weights whose rows carry folded latent columns after the per-sample ones
   a.ldw[A_D0] = (int)prm->w_cols[kArtDef0];
   a.ldw[A_P0] = (int)prm->w_cols[kArtPts0];
   a.ldw[A_P5] = (int)prm->w_cols[kArtPts5];
   a.ldw[A_V0] = (int)prm->w_cols[kArtView0];
-  a.n_layers = kNumLayersArt;
-  a.stream_blocks = NetArtH::kStreamBlocks;
-  a.bias_floats = NetArtH::kBiasFloats;
   if (mixed) {
     const StreamMap m = mixed == 2 ? kArtMixV : kArtMix;
     a.bf16 = m.mode;
@@ -309,27 +297,21 @@ static int art_launch(int mode, const void* packed, const float* a0, const float
                       const float* a2, const float* a3, int64_t B, int S, int act, float* raw,
                       aon_stream_t stream) {
   AON_REQUIRE(packed && raw && a0 && a1, "null pointer");
-  AON_REQUIRE(B >= 0 && S >= 1, "bad shape");
-  AON_REQUIRE(act >= AON_ACT_NONE && act <= AON_ACT_ARTIC, "bad activation");
-  AON_REQUIRE(aligned16(packed) && aligned16(raw), "packed / raw must be 16-byte aligned");
+  if (check_fwd_args(__func__, packed, raw, B, S, act)) return -1;
   const int64_t N = B * S;
   if (N == 0) return 0;
   using G = GeomH<1>;
-  const int64_t grid = (N + G::kRowsPerBlock - 1) / G::kRowsPerBlock;
-  AON_REQUIRE(grid < (1ll << 31), "too many rows");
+  AON_REQUIRE(rows_ok(N), "too many rows");
+  static_assert(kRowsOkCovers<G>, "rows_ok covers this grid");
+  const unsigned grid = chain_grid<G>(N);
   const f4* ws = static_cast<const f4*>(packed);
-  const float* bias =
-      reinterpret_cast<const float*>(static_cast<const char*>(packed) + NetArtH::kStreamBytes);
+  const float* bias = stream_bias<NetArtH>(packed);
 #if AON_DATAFLOW_WS_BUILD
   if (mode == 0)
     return launch_art_ws_f16x3(packed, a0, a1, a2, a3, B, S, act, raw, (hipStream_t)stream);
 #endif
-  if (mode == 0)
-    hipLaunchKernelGGL((k_mlp_art_f16x3<0, 1>), (unsigned)grid, G::kThreads, 0,
-                       (hipStream_t)stream, ws, bias, a0, a1, a2, a3, B, S, act, raw);
-  else
-    hipLaunchKernelGGL((k_mlp_art_f16x3<1, 1>), (unsigned)grid, G::kThreads, 0,
-                       (hipStream_t)stream, ws, bias, a0, a1, a2, a3, B, S, act, raw);
+  hipLaunchKernelGGL((mode == 0 ? k_mlp_art_f16x3<0, 1> : k_mlp_art_f16x3<1, 1>), grid, G::kThreads,
+                     0, (hipStream_t)stream, ws, bias, a0, a1, a2, a3, B, S, act, raw, TrainStoreArt{});
   return launch_status("aon_mlp_art_fwd");
 }
 
@@ -343,6 +325,18 @@ extern "C" int aon_mlp_art_fwd(const void* packed, const float* rays_o, const fl
 #ifndef AON_ART_X1_NCOL
 #define AON_ART_X1_NCOL 1  // A/B knob (compile-time): samples per wave / 16 of the mixed-4 forward
 #endif
+// one launch of the training forward k_mlp_art_f16x3<0, NCOL, true, PREC>
+template <int PREC, int NCOL>
+static void launch_art_train(const void* packed, const float* rays_o, const float* rays_d,
+                             const float* viewdirs, const float* t, int64_t B, int S, float* raw,
+                             const TrainStoreArt& ts, hipStream_t stream) {
+  using G = GeomH<NCOL>;
+  static_assert(kRowsOkCovers<G>, "art_fwd_train's rows_ok covers this grid");
+  hipLaunchKernelGGL((k_mlp_art_f16x3<0, NCOL, true, PREC>), chain_grid<G>(B * S), G::kThreads, 0,
+                     stream, static_cast<const f4*>(packed), stream_bias<NetArtH>(packed), rays_o,
+                     rays_d, viewdirs, t, B, S, (int)AON_ACT_NONE, raw, ts);
+}
+
 static int art_fwd_train(const void* packed, const float* rays_o, const float* rays_d,
                          const float* viewdirs, const float* t, int64_t B, int S,
                          const float* noise, float* hd, float* h, float* bot, float* hv,
@@ -352,46 +346,23 @@ static int art_fwd_train(const void* packed, const float* rays_o, const float* r
   AON_REQUIRE(hd && h && bot && hv && enc && xyz && masks, "null activation buffer");
   AON_REQUIRE(aligned16(masks) && aligned16(enc), "masks / enc must be 16-byte aligned");
   AON_REQUIRE(!prec || (enc_bf && aligned16(enc_bf)), "enc_bf: a 16-byte aligned buffer");
-  AON_REQUIRE(B >= 0 && S >= 1, "bad shape");
-  AON_REQUIRE(aligned16(packed) && aligned16(raw), "packed / raw must be 16-byte aligned");
+  if (check_fwd_args(__func__, packed, raw, B, S, AON_ACT_NONE)) return -1;
   AON_REQUIRE(((reinterpret_cast<uintptr_t>(hd) | reinterpret_cast<uintptr_t>(h) |
                 reinterpret_cast<uintptr_t>(bot) | reinterpret_cast<uintptr_t>(hv)) & 7) == 0,
               "activation buffers must be 8-byte aligned");
-  const int64_t N = B * S;
-  if (N == 0) return 0;
-  using G = GeomH<1>;
-  const int64_t grid = (N + G::kRowsPerBlock - 1) / G::kRowsPerBlock;
-  AON_REQUIRE(grid < (1ll << 31), "too many rows");
-  const f4* ws = static_cast<const f4*>(packed);
-  const float* bias =
-      reinterpret_cast<const float*>(static_cast<const char*>(packed) + NetArtH::kStreamBytes);
+  if (B * S == 0) return 0;
+  AON_REQUIRE(rows_ok(B * S), "too many rows");
   const TrainStoreArt ts{hd, h, bot, hv, enc, xyz, noise, reinterpret_cast<uint2*>(masks), enc_bf};
-  if (prec == 5) {
-    using G5 = GeomH<AON_ART_X1_NCOL>;
-    hipLaunchKernelGGL((k_mlp_art_f16x3<0, AON_ART_X1_NCOL, true, 5>),
-                       (unsigned)((N + G5::kRowsPerBlock - 1) / G5::kRowsPerBlock), G5::kThreads, 0,
-                       (hipStream_t)stream, ws, bias, rays_o, rays_d, viewdirs, t, B, S,
-                       (int)AON_ACT_NONE, raw, ts);
-  } else if (prec == 4)
-    hipLaunchKernelGGL((k_mlp_art_f16x3<0, 1, true, 4>), (unsigned)grid, G::kThreads, 0,
-                       (hipStream_t)stream, ws, bias, rays_o, rays_d, viewdirs, t, B, S,
-                       (int)AON_ACT_NONE, raw, ts);
-  else if (prec == 3)
-    hipLaunchKernelGGL((k_mlp_art_f16x3<0, 1, true, 3>), (unsigned)grid, G::kThreads, 0,
-                       (hipStream_t)stream, ws, bias, rays_o, rays_d, viewdirs, t, B, S,
-                       (int)AON_ACT_NONE, raw, ts);
-  else if (prec == 2)
-    hipLaunchKernelGGL((k_mlp_art_f16x3<0, 1, true, 2>), (unsigned)grid, G::kThreads, 0,
-                       (hipStream_t)stream, ws, bias, rays_o, rays_d, viewdirs, t, B, S,
-                       (int)AON_ACT_NONE, raw, ts);
-  else if (prec == 1)
-    hipLaunchKernelGGL((k_mlp_art_f16x3<0, 1, true, 1>), (unsigned)grid, G::kThreads, 0,
-                       (hipStream_t)stream, ws, bias, rays_o, rays_d, viewdirs, t, B, S,
-                       (int)AON_ACT_NONE, raw, ts);
-  else
-    hipLaunchKernelGGL((k_mlp_art_f16x3<0, 1, true>), (unsigned)grid, G::kThreads, 0,
-                       (hipStream_t)stream, ws, bias, rays_o, rays_d, viewdirs, t, B, S,
-                       (int)AON_ACT_NONE, raw, ts);
+  decltype(&launch_art_train<0, 1>) launch;
+  switch (prec) {  // k_mlp_art_f16x3's PREC
+    case 5: launch = launch_art_train<5, AON_ART_X1_NCOL>; break;
+    case 4: launch = launch_art_train<4, 1>; break;
+    case 3: launch = launch_art_train<3, 1>; break;
+    case 2: launch = launch_art_train<2, 1>; break;
+    case 1: launch = launch_art_train<1, 1>; break;
+    default: launch = launch_art_train<0, 1>; break;
+  }
+  launch(packed, rays_o, rays_d, viewdirs, t, B, S, raw, ts, (hipStream_t)stream);
   return launch_status(prec ? "aon_mlp_art_fwd_train_bf16" : "aon_mlp_art_fwd_train");
 }
 

@@ -359,6 +359,7 @@ static int art_bwd_pack(const aon_mlp_art_params* prm, void* packed, aon_stream_
   const int ld_view0 = (int)prm->w_cols[kArtView0], ld_pts5 = (int)prm->w_cols[kArtPts5];
   const int ld_pts0 = (int)prm->w_cols[kArtPts0];
   PackArgsH a{};
+  fill_net<NetArtBwdH>(a);
   const float* w[kNumLayersArtBwd] = {
       prm->rgb_w,     prm->views_w[3], prm->views_w[2], prm->views_w[1], prm->views_w[0],
       prm->bottleneck_w, prm->pts_w[7], prm->pts_w[6], prm->pts_w[5],
@@ -373,14 +374,10 @@ static int art_bwd_pack(const aon_mlp_art_params* prm, void* packed, aon_stream_
     a.w[i] = w[i];
     a.ldw[i] = ld[i];
     a.tr[i] = 1;
-    a.layers[i] = kLayersArtBwd[i];
   }
   AON_REQUIRE(prm->density_w, "null layer weight");
   a.w2[AB_BOTDEN] = prm->density_w;  // segment B of d h7: density_layer^T (1 x 256)
   a.ldw2[AB_BOTDEN] = 256;
-  a.n_layers = kNumLayersArtBwd;
-  a.stream_blocks = NetArtBwdH::kStreamBlocks;
-  a.bias_floats = NetArtBwdH::kBiasFloats;
   a.bf16 = bf16 ? 1 : 0;
   return pack_h(a, packed, (hipStream_t)stream);
 }
@@ -405,9 +402,9 @@ static int art_bwd(const void* packed, const float* draw, const uint32_t* masks,
                   aligned16(dbot) && aligned16(dz) && aligned16(dzd),
               "buffers must be 16-byte aligned");
   if (N == 0) return 0;
-  const int64_t rpb = bf16 ? ArtBwdGeom<true>::kRowsPerBlock : ArtBwdGeom<false>::kRowsPerBlock;
-  const int64_t grid = (N + rpb - 1) / rpb;
-  AON_REQUIRE(grid < (1ll << 31), "too many rows");
+  using G1 = ArtBwdGeom<false>;
+  using GB = ArtBwdGeom<true>;
+  AON_REQUIRE(bf16 ? rows_ok<GB>(N) : rows_ok<G1>(N), "too many rows");
   hipStream_t st = (hipStream_t)stream;
   uint32_t* amax = static_cast<uint32_t*>(work);
   // the fp16x3 chain's per-call gradient scale (bf16 runs unscaled: no max pass)
@@ -416,14 +413,13 @@ static int art_bwd(const void* packed, const float* draw, const uint32_t* masks,
   const ArtBwdArgs args{draw, reinterpret_cast<const uint2*>(masks), enc, dzv, dbot, dz, dxp, dzd,
                         amax, N};
   const f4* wsp = static_cast<const f4*>(packed);
-  const float* bias =
-      reinterpret_cast<const float*>(static_cast<const char*>(packed) + NetArtBwdH::kStreamBytes);
+  const float* bias = stream_bias<NetArtBwdH>(packed);
   if (bf16)
-    hipLaunchKernelGGL(k_mlp_art_bwd_f16x3<true>, (unsigned)grid, ArtBwdGeom<true>::kThreads, 0, st,
-                       wsp, bias, args);
+    hipLaunchKernelGGL(k_mlp_art_bwd_f16x3<true>, chain_grid<GB>(N), GB::kThreads, 0, st, wsp, bias,
+                       args);
   else
-    hipLaunchKernelGGL(k_mlp_art_bwd_f16x3<false>, (unsigned)grid, ArtBwdGeom<false>::kThreads, 0,
-                       st, wsp, bias, args);
+    hipLaunchKernelGGL(k_mlp_art_bwd_f16x3<false>, chain_grid<G1>(N), G1::kThreads, 0, st, wsp, bias,
+                       args);
   return launch_status(bf16 ? "aon_mlp_art_bwd_bf16" : "aon_mlp_art_bwd");
 }
 

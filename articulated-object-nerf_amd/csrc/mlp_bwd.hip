@@ -180,6 +180,7 @@ static int bwd_pack(const aon_mlp_params* prm, void* packed, aon_stream_t stream
   AON_REQUIRE(aligned16(packed), "packed buffer must be 16-byte aligned");
   if (check_mlp_params(prm, bf16 ? "aon_mlp_bwd_pack_bf16" : "aon_mlp_bwd_pack")) return -1;
   PackArgsH a{};
+  fill_net<NetBwdH>(a);
   const float* w[kNumLayersBwd] = {prm->rgb_w,    prm->views_w,  prm->bottleneck_w,
                                    prm->pts_w[7], prm->pts_w[6], prm->pts_w[5],
                                    prm->pts_w[4], prm->pts_w[3], prm->pts_w[2],
@@ -191,14 +192,10 @@ static int bwd_pack(const aon_mlp_params* prm, void* packed, aon_stream_t stream
     a.w[i] = w[i];
     a.ldw[i] = ld[i];
     a.tr[i] = 1;
-    a.layers[i] = kLayersBwd[i];
   }
   AON_REQUIRE(prm->density_w, "null layer weight");
   a.w2[B_BOTDEN] = prm->density_w;  // segment B of d h7: density_layer^T (1 x 256)
   a.ldw2[B_BOTDEN] = 256;
-  a.n_layers = kNumLayersBwd;
-  a.stream_blocks = NetBwdH::kStreamBlocks;
-  a.bias_floats = NetBwdH::kBiasFloats;
   a.bf16 = bf16 ? 1 : 0;
   return pack_h(a, packed, (hipStream_t)stream);
 }
@@ -222,9 +219,7 @@ static int bwd_launch(const void* packed, const float* draw, const uint32_t* mas
   if (N == 0) return 0;
   using G1 = GeomH<1>;
   using GB = GeomH<kBfNcolBwd, true>;
-  const int64_t rpb = bf16 ? GB::kRowsPerBlock : G1::kRowsPerBlock;
-  const int64_t grid = (N + rpb - 1) / rpb;
-  AON_REQUIRE(grid < (1ll << 31), "too many rows");
+  AON_REQUIRE(bf16 ? rows_ok<GB>(N) : rows_ok<G1>(N), "too many rows");
   hipStream_t st = (hipStream_t)stream;
   uint32_t* amax = static_cast<uint32_t*>(work);
   // the fp16x3 chain's per-call gradient scale (bf16 runs unscaled: no max pass)
@@ -233,12 +228,11 @@ static int bwd_launch(const void* packed, const float* draw, const uint32_t* mas
   BwdArgs args{draw, reinterpret_cast<const uint2*>(masks), static_cast<float*>(dzv),
                static_cast<float*>(dzb), static_cast<float*>(dz), amax, N};
   const f4* ws = static_cast<const f4*>(packed);
-  const float* bias =
-      reinterpret_cast<const float*>(static_cast<const char*>(packed) + NetBwdH::kStreamBytes);
+  const float* bias = stream_bias<NetBwdH>(packed);
   if (bf16)
-    hipLaunchKernelGGL(k_mlp_bwd_f16x3<true>, (unsigned)grid, GB::kThreads, 0, st, ws, bias, args);
+    hipLaunchKernelGGL(k_mlp_bwd_f16x3<true>, chain_grid<GB>(N), GB::kThreads, 0, st, ws, bias, args);
   else
-    hipLaunchKernelGGL(k_mlp_bwd_f16x3<false>, (unsigned)grid, G1::kThreads, 0, st, ws, bias, args);
+    hipLaunchKernelGGL(k_mlp_bwd_f16x3<false>, chain_grid<G1>(N), G1::kThreads, 0, st, ws, bias, args);
   return launch_status(bf16 ? "aon_mlp_bwd_bf16" : "aon_mlp_bwd");
 }
 

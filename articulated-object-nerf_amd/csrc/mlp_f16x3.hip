@@ -144,26 +144,18 @@ __global__ __launch_bounds__((GeomH<NCOL, BF>::kThreads), (GeomH<NCOL, BF>::kWav
   using G = GeomH<NCOL, BF>;
   constexpr bool SIG = kSigmaOnly<Net>;
   static_assert(!SIG || MODE == 0, "the density-only pass takes MODE 0 inputs");
-  // ONE __shared__ object: weight ring | bias table | per-lane stash of the encodings
-  constexpr int kPer = stash_per<BF, SIG>() * NCOL;  // f4 per lane: enc 2 k-steps + venc 1, hi (& lo)
-  constexpr int kStash = G::kWaves * 64 * kPer;
-  static_assert((kLdsWeights + Net::kBiasFloats / 4 + kStash) * 16 <= 160 * 1024, "LDS");
-  __shared__ f4 smem[kLdsWeights + Net::kBiasFloats / 4 + kStash];
-  float* bias_s = reinterpret_cast<float*>(smem + kLdsWeights);
-  f4* stash = smem + kLdsWeights + Net::kBiasFloats / 4 + (threadIdx.x >> 6) * 64 * kPer +
-              (threadIdx.x & 63);  // lane-private slots: written and read by the same lane
+  // the per-lane stash of the encodings: enc 2 k-steps + venc 1, hi (& lo)
+  using Lds = ChainLds<Net, G, stash_per<BF, SIG>() * NCOL>;
+  __shared__ f4 smem[Lds::kF4];
+  float* bias_s = Lds::bias(smem);
+  f4* stash = Lds::stash(smem);
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, j = lane & 15;
   const int64_t N = B * S;
 
   WeightPipeP<Net, G::kThreads, BF> p;
-  p.wbuf = smem;
-  p.src = wstream;
-  p.tid = tid;
-  p.lane = lane;
-  p.start();
-  for (int i = tid; i < Net::kBiasFloats; i += G::kThreads) bias_s[i] = bias_g[i];
+  start_chain<Net, G::kThreads>(p, smem, wstream, tid, lane, bias_s, bias_g);
 
   // layer-0 (enc) and view-layer (enc_dir) fragments: k-step k, lane group g, element e
   // <-> feature 32k + 8g + e of the encoding
@@ -418,95 +410,68 @@ int pack_f16x3(const PackArgs& a, void* packed, hipStream_t stream, bool bf16, b
   h.bf16 = bf16 ? 1 : 0;
   if (fold) {
     // the render stream: kLayersH without the bottleneck, folded into the view layer
-    for (int i = 0; i < kNumLayersFold; ++i) {
-      const int src = i < LBOT ? i : i + 1;
-      h.w[i] = a.w[src];
-      h.b[i] = a.b[src];
-      h.layers[i] = kLayersHFold[i];
-      h.ldw[i] = kLayersHFold[i].len_a + kLayersHFold[i].len_b;
-    }
+    fill_net<NetVanillaFoldH>(h);
     h.fold_w = a.w[LBOT];
     h.fold_b = a.b[LBOT];
     h.fold_layer = LF_VIEW;
     h.fold_k = kLayersH[LBOT].out_real;
-    h.n_layers = kNumLayersFold;
-    h.stream_blocks = NetVanillaFoldH::kStreamBlocks;
-    h.bias_floats = NetVanillaFoldH::kBiasFloats;
-    return pack_h(h, packed, stream);
+  } else {
+    fill_net<NetVanillaH>(h);
   }
-  for (int i = 0; i < kNumLayers; ++i) {
-    h.w[i] = a.w[i];
-    h.b[i] = a.b[i];
-    h.layers[i] = kLayersH[i];
-    h.ldw[i] = kLayersH[i].len_a + kLayersH[i].len_b;
+  for (int i = 0; i < h.n_layers; ++i) {
+    const int src = fold && i >= LBOT ? i + 1 : i;
+    h.w[i] = a.w[src];
+    h.b[i] = a.b[src];
   }
-  h.n_layers = kNumLayers;
-  h.stream_blocks = NetVanillaH::kStreamBlocks;
-  h.bias_floats = NetVanillaH::kBiasFloats;
   return pack_h(h, packed, stream);
 }
 
-int launch_f16x3(int mode, int ncol, const void* packed, const float* a0, const float* a1,
-                 const float* a2, const float* a3, int64_t B, int S, int act, float* raw,
-                 hipStream_t stream, const TrainStore* ts) {
-  const int64_t N = B * S;
-  const f4* ws = static_cast<const f4*>(packed);
-  // the training forwards read the unfolded stream, the render the folded one
-  const bool train = mode == 2 || mode == 3;
-  const float* bias = reinterpret_cast<const float*>(
-      static_cast<const char*>(packed) +
-      (train ? NetVanillaH::kStreamBytes : NetVanillaFoldH::kStreamBytes));
-#define AON_LAUNCH_H(M, C)                                                                       \
-  hipLaunchKernelGGL((k_mlp_fwd_f16x3<M, C, false, false, NetVanillaFoldH>),                     \
-                     static_cast<int>((N + GeomH<C>::kRowsPerBlock - 1) / GeomH<C>::kRowsPerBlock), \
-                     GeomH<C>::kThreads, 0, stream, ws, bias, a0, a1, a2, a3, B, S, act, raw)
-  if (train) {  // training forward: MODE 0 inputs + activation stores
-    const int grid = static_cast<int>((N + GeomH<1>::kRowsPerBlock - 1) / GeomH<1>::kRowsPerBlock);
-    if (mode == 3) {  // bf16 training mode: 16 kBfNcolFwd samples per wave
-      using GB = GeomH<kBfNcolFwd, true>;
-      hipLaunchKernelGGL((k_mlp_fwd_f16x3<0, kBfNcolFwd, true, true>),
-                         static_cast<int>((N + GB::kRowsPerBlock - 1) / GB::kRowsPerBlock),
-                         GB::kThreads, 0, stream, ws, bias, a0, a1, a2, a3, B, S, act, raw, *ts);
-    } else
-      hipLaunchKernelGGL((k_mlp_fwd_f16x3<0, 1, true>), grid, GeomH<1>::kThreads, 0, stream, ws,
-                         bias, a0, a1, a2, a3, B, S, act, raw, *ts);
-    return launch_status("aon_mlp_fwd_train");
-  }
-  if (mode == 0 && ncol == 1) AON_LAUNCH_H(0, 1);
-  else if (mode == 0) AON_LAUNCH_H(0, 2);
-  else if (ncol == 1) AON_LAUNCH_H(1, 1);
-  else AON_LAUNCH_H(1, 2);
-#undef AON_LAUNCH_H
-  return launch_status("aon_mlp_fwd");
+// one launch of k_mlp_fwd_f16x3<MODE, NCOL, STORE, BF, Net>, reported as fn (the density-only
+// pass reads a prefix of the render pack: its bias table sits behind the whole folded stream)
+template <int MODE, int NCOL, bool STORE, bool BF, typename Net>
+static int launch_fwd(const char* fn, const void* packed, const float* a0, const float* a1,
+                      const float* a2, const float* a3, int64_t B, int S, int act, float* raw,
+                      hipStream_t stream, const TrainStore& ts = {}) {
+  using G = GeomH<NCOL, BF>;
+  using Packed = typename std::conditional<kSigmaOnly<Net>, NetVanillaFoldH, Net>::type;
+  static_assert(kRowsOkCovers<G>, "the callers' rows_ok covers this grid");
+  hipLaunchKernelGGL((k_mlp_fwd_f16x3<MODE, NCOL, STORE, BF, Net>), chain_grid<G>(B * S),
+                     G::kThreads, 0, stream, static_cast<const f4*>(packed),
+                     stream_bias<Packed>(packed), a0, a1, a2, a3, B, S, act, raw, ts);
+  return launch_status(fn);
 }
 
-// the render stream's bias table (and, behind it, the status word)
-static const float* fold_bias(const void* packed) {
-  return reinterpret_cast<const float*>(static_cast<const char*>(packed) +
-                                        NetVanillaFoldH::kStreamBytes);
+int launch_f16x3_train(bool bf16, const TrainStore& ts, const void* packed, const float* rays_o,
+                       const float* rays_d, const float* viewdirs, const float* t, int64_t B,
+                       int S, float* raw, hipStream_t stream) {
+  // (the bf16 training mode: 16 kBfNcolFwd samples per wave)
+  const auto launch = bf16 ? launch_fwd<0, kBfNcolFwd, true, true, NetVanillaH>
+                           : launch_fwd<0, 1, true, false, NetVanillaH>;
+  return launch("aon_mlp_fwd_train", packed, rays_o, rays_d, viewdirs, t, B, S, AON_ACT_NONE, raw,
+                stream, ts);
+}
+
+int launch_f16x3_render(bool encoded, int ncol, const void* packed, const float* a0,
+                        const float* a1, const float* a2, const float* a3, int64_t B, int S,
+                        int act, float* raw, hipStream_t stream) {
+  using Net = NetVanillaFoldH;
+  const auto launch =
+      !encoded ? (ncol == 1 ? launch_fwd<0, 1, false, false, Net> : launch_fwd<0, 2, false, false, Net>)
+               : (ncol == 1 ? launch_fwd<1, 1, false, false, Net> : launch_fwd<1, 2, false, false, Net>);
+  return launch("aon_mlp_fwd", packed, a0, a1, a2, a3, B, S, act, raw, stream, TrainStore{});
 }
 
 int launch_f16x3_sigma(const void* packed, const float* rays_o, const float* rays_d,
                        const float* t, int64_t B, int S, int act, float* raw, hipStream_t stream) {
-  using G = GeomH<1>;
-  const int64_t N = B * S;
-  hipLaunchKernelGGL((k_mlp_fwd_f16x3<0, 1, false, false, NetVanillaSigmaH>),
-                     static_cast<int>((N + G::kRowsPerBlock - 1) / G::kRowsPerBlock), G::kThreads, 0,
-                     stream, static_cast<const f4*>(packed), fold_bias(packed), rays_o, rays_d,
-                     static_cast<const float*>(nullptr), t, B, S, act, raw);
-  return launch_status("aon_mlp_fwd_sigma");
+  return launch_fwd<0, 1, false, false, NetVanillaSigmaH>("aon_mlp_fwd_sigma", packed, rays_o,
+                                                          rays_d, nullptr, t, B, S, act, raw, stream);
 }
 
 int launch_f16x3_cond(const void* packed, const float* rays_o, const float* rays_d,
                       const float* cond, const float* t, int64_t B, int S, int act, float* raw,
                       hipStream_t stream) {
-  using G = GeomH<1>;
-  const int64_t N = B * S;
-  hipLaunchKernelGGL((k_mlp_fwd_f16x3<2, 1, false, false, NetVanillaFoldH>),
-                     static_cast<int>((N + G::kRowsPerBlock - 1) / G::kRowsPerBlock), G::kThreads, 0,
-                     stream, static_cast<const f4*>(packed), fold_bias(packed), rays_o, rays_d, cond,
-                     t, B, S, act, raw);
-  return launch_status("aon_mlp_fwd_cond");
+  return launch_fwd<2, 1, false, false, NetVanillaFoldH>("aon_mlp_fwd_cond", packed, rays_o, rays_d,
+                                                         cond, t, B, S, act, raw, stream);
 }
 
 }  // namespace mlp

@@ -834,28 +834,36 @@ using WeightPipeP = typename std::conditional<
     WeightPipe<Net, THREADS>>::type;
 constexpr int kLdsWeights = kRing * kChunkH * 64;  // f4
 
-#ifndef AON_WAVES_H
-#define AON_WAVES_H 8  // waves per workgroup at 16 samples per wave (2 waves per SIMD either way)
-#endif
+// ---- the set-up a chain kernel opens with (mlp_f16x3.hip, mlp_art.hip); a new chain kernel
+// starts from these
 
-// BF: the bf16 training kernels -- at 32 samples per wave (NCOL = 2) they keep 8 waves (2 per
-// SIMD): bf16 activations carry no lo part, so a wave's input and output fragments take 64 + 64
-// VGPRs where fp16x3 needs 256 (its NCOL = 2 runs 4 waves, one per SIMD)
-#ifndef AON_BF_NCOL_FWD
-#define AON_BF_NCOL_FWD 1  // samples per wave / 16 of the bf16 training forward
-#endif
-#ifndef AON_BF_NCOL_BWD
-#define AON_BF_NCOL_BWD 2  // ... and of the bf16 backward chain
-#endif
-constexpr int kBfNcolFwd = AON_BF_NCOL_FWD, kBfNcolBwd = AON_BF_NCOL_BWD;
-template <int NCOL, bool BF = false>
-struct GeomH {
-  static constexpr int kWaves = (NCOL == 1 || BF) ? AON_WAVES_H : 4;
-  static constexpr int kThreads = 64 * kWaves;
-  static constexpr int kRowsPerWave = 16 * NCOL;
-  static constexpr int kRowsPerBlock = kRowsPerWave * kWaves;
-  static constexpr int kWavesPerSimd = kWaves / 4;  // __launch_bounds__' occupancy request
+// The ONE __shared__ object of a chain kernel, f4 smem[kF4]: weight ring | bias table | kPerLane
+// lane-private f4 slots per lane (written and read by the same lane; slot i at stash(smem)[64 i])
+template <typename Net, typename G, int kPerLane>
+struct ChainLds {
+  static constexpr int kBiasAt = kLdsWeights;
+  static constexpr int kStashAt = kBiasAt + Net::kBiasFloats / 4;
+  static constexpr int kF4 = kStashAt + G::kWaves * 64 * kPerLane;
+  static_assert(kF4 * 16 <= 160 * 1024, "LDS");
+  __device__ __forceinline__ static float* bias(f4* smem) { return reinterpret_cast<float*>(smem + kBiasAt); }
+  __device__ __forceinline__ static f4* stash(f4* smem) {
+    return smem + kStashAt + (threadIdx.x >> 6) * 64 * kPerLane + (threadIdx.x & 63);
+  }
 };
+
+// the weight pipe over the ring at smem started on its first chunks, and the bias table copied to
+// LDS (published by the barrier of the pipe's first begin: FragPipe::start)
+template <typename Net, int THREADS, typename P>
+__device__ __forceinline__ void start_chain(P& p, f4* smem, const f4* __restrict__ wstream,
+                                            int tid, int lane, float* bias_s,
+                                            const float* __restrict__ bias_g) {
+  p.wbuf = smem;
+  p.src = wstream;
+  p.tid = tid;
+  p.lane = lane;
+  p.start();
+  for (int i = tid; i < Net::kBiasFloats; i += THREADS) bias_s[i] = bias_g[i];
+}
 
 }  // namespace mlp
 }  // namespace aon

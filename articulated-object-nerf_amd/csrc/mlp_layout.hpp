@@ -399,7 +399,7 @@ static_assert(kLayersArt[A_V0].blk0 == kArtMixV.hi && kArtMixV.map(2408) == 2408
                   kArtMixV.unmap(kArtMixV.map(2750)) == 2750,
               "view-branch stream map");
 
-// Training forward of the fused kernel (launch_f16x3 mode 2): every hidden activation goes to
+// Training forward of the fused kernel (launch_f16x3_train): every hidden activation goes to
 // HBM for the backward, as the layer-by-layer path keeps them: h (8, N, 256) post-ReLU
 // pts_linears outputs, bot (N, 256), hv (N, 128) post-ReLU views_linear.0; raw_sigma gets
 // + noise[row] when noise is set (model.py:183-184).
@@ -425,6 +425,64 @@ struct TrainStoreArt {
   __bf16* enc_bf;      // bf16 modes, optional: pos_enc(x') tiled (N, 128), columns 63.. zero
 };
 
+// ---- workgroup geometry of the chain kernels
+#ifndef AON_WAVES_H
+#define AON_WAVES_H 8  // waves per workgroup at 16 samples per wave (2 waves per SIMD either way)
+#endif
+
+// BF: the bf16 training kernels -- at 32 samples per wave (NCOL = 2) they keep 8 waves (2 per
+// SIMD): bf16 activations carry no lo part, so a wave's input and output fragments take 64 + 64
+// VGPRs where fp16x3 needs 256 (its NCOL = 2 runs 4 waves, one per SIMD)
+#ifndef AON_BF_NCOL_FWD
+#define AON_BF_NCOL_FWD 1  // samples per wave / 16 of the bf16 training forward
+#endif
+#ifndef AON_BF_NCOL_BWD
+#define AON_BF_NCOL_BWD 2  // ... and of the bf16 backward chain
+#endif
+constexpr int kBfNcolFwd = AON_BF_NCOL_FWD, kBfNcolBwd = AON_BF_NCOL_BWD;
+template <int NCOL, bool BF = false>
+struct GeomH {
+  static constexpr int kWaves = (NCOL == 1 || BF) ? AON_WAVES_H : 4;
+  static constexpr int kThreads = 64 * kWaves;
+  static constexpr int kRowsPerWave = 16 * NCOL;
+  static constexpr int kRowsPerBlock = kRowsPerWave * kWaves;
+  static constexpr int kWavesPerSimd = kWaves / 4;  // __launch_bounds__' occupancy request
+};
+
+// ---- host side of every chain launch (G: a geometry with kRowsPerBlock; Net: the stream read)
+template <typename G>
+inline int64_t chain_grid(int64_t N) { return (N + G::kRowsPerBlock - 1) / G::kRowsPerBlock; }
+// the "too many rows" guard: the grid fits 31 bits.  The forwards test GeomH<1> whatever they
+// launch; static_assert(kRowsOkCovers<G>) beside a launch says that its grid is no larger.
+template <typename G = GeomH<1>>
+inline bool rows_ok(int64_t N) { return chain_grid<G>(N) < (1ll << 31); }
+template <typename G>
+constexpr bool kRowsOkCovers = G::kRowsPerBlock >= GeomH<1>::kRowsPerBlock;
+// the bias table (and, behind it, the status word) of a packed Net stream
+template <typename Net>
+inline const float* stream_bias(const void* packed) {
+  return reinterpret_cast<const float*>(static_cast<const char*>(packed) + Net::kStreamBytes);
+}
+// the shape / activation / alignment checks of the render and training forwards, reported as fn
+inline int check_fwd_args(const char* fn, const void* packed, const void* raw, int64_t B, int S,
+                          int act) {
+  AON_REQUIRE_AS(fn, B >= 0 && S >= 1, "bad shape");
+  AON_REQUIRE_AS(fn, act >= AON_ACT_NONE && act <= AON_ACT_ARTIC, "bad activation");
+  AON_REQUIRE_AS(fn, aligned16(packed) && aligned16(raw), "packed / raw must be 16-byte aligned");
+  return 0;
+}
+// a Net's layer table, stream geometry and default row strides (len_a + len_b) into pack args
+template <typename Net>
+inline void fill_net(PackArgsH& a) {
+  for (int i = 0; i < Net::kNumLayers; ++i) {
+    a.layers[i] = Net::layer(i);
+    a.ldw[i] = Net::layer(i).len_a + Net::layer(i).len_b;
+  }
+  a.n_layers = Net::kNumLayers;
+  a.stream_blocks = Net::kStreamBlocks;
+  a.bias_floats = Net::kBiasFloats;
+}
+
 // fp16x3 path (mlp_f16x3.hip)
 // fold: the render stream (NetVanillaFoldH), else the training forwards' (NetVanillaH)
 int pack_f16x3(const PackArgs& a, void* packed, hipStream_t stream, bool bf16 = false,
@@ -433,20 +491,26 @@ int pack_h(PackArgsH a, void* packed, hipStream_t stream);
 // *out = bits of max |x| over n floats (memset + k_absmax, mlp_bwd.hip): the backward chains'
 // per-call gradient scale
 int absmax(const float* x, int64_t n, uint32_t* out, hipStream_t stream);
-int launch_f16x3(int mode, int ncol, const void* packed, const float* a0, const float* a1,
-                 const float* a2, const float* a3, int64_t B, int S, int act, float* raw,
-                 hipStream_t stream, const TrainStore* ts = nullptr);
+// the render forward (folded stream): kernel MODE 0, or MODE 1 (encoded); 16 ncol samples per wave
+int launch_f16x3_render(bool encoded, int ncol, const void* packed, const float* a0,
+                        const float* a1, const float* a2, const float* a3, int64_t B, int S,
+                        int act, float* raw, hipStream_t stream);
+// the training forward (MODE 0 inputs, AON_ACT_NONE, activations kept in ts): fp16x3 or bf16
+int launch_f16x3_train(bool bf16, const TrainStore& ts, const void* packed, const float* rays_o,
+                       const float* rays_d, const float* viewdirs, const float* t, int64_t B,
+                       int S, float* raw, hipStream_t stream);
 // the render stream's two-pass entry points (16 samples per wave): the density-only pass
 // (NetVanillaSigmaH: raw rows {0, 0, 0, sigma}) and the conditioned forward (kernel MODE 2: the
-// view encodings from a (B, 27) table) -- column 3 / all of launch_f16x3 mode 0, bit for bit
+// view encodings from a (B, 27) table) -- column 3 / all of launch_f16x3_render's MODE 0, bit
+// for bit
 int launch_f16x3_sigma(const void* packed, const float* rays_o, const float* rays_d,
                        const float* t, int64_t B, int S, int act, float* raw, hipStream_t stream);
 int launch_f16x3_cond(const void* packed, const float* rays_o, const float* rays_d,
                       const float* cond, const float* t, int64_t B, int S, int act, float* raw,
                       hipStream_t stream);
 // the weight-streamed fp16x3 render forward (mlp_ws.hip; MODE 0 inputs, bit-identical to
-// launch_f16x3 mode 0) -- an A/B variant, not in the release library: `make variant-ws` builds
-// lib/variants/libaonerf_ws.so with AON_DATAFLOW_WS_BUILD = 1, whose render forwards
+// launch_f16x3_render's MODE 0) -- an A/B variant, not in the release library: `make variant-ws`
+// builds lib/variants/libaonerf_ws.so with AON_DATAFLOW_WS_BUILD = 1, whose render forwards
 // (aon_mlp_fwd, aon_mlp_art_fwd) take this dataflow; the release build has no process-global
 // kernel selection and no environment knobs
 #ifndef AON_DATAFLOW_WS_BUILD

@@ -42,6 +42,7 @@ struct Geo {
   static constexpr int kThreads = 64 * kWaves;
   static constexpr int kTiles = kWaves;             // 16-sample tiles per workgroup pass
   static constexpr int kNb = 16 * kTiles;           // samples per pass
+  static constexpr int kRowsPerBlock = kNb;         // rows a workgroup covers
   static constexpr int kActPlane = 8 * 4 * kNb;     // f4: [k-step 8][lane group 4][sample]
   static constexpr int kEncPlane = 2 * 4 * kNb;     // f4: segment B, 2 k-steps
   static constexpr int kLdsF4 = 2 * kActPlane + 2 * kEncPlane;
@@ -488,22 +489,19 @@ __global__ __launch_bounds__(Geo::kThreads, Geo::kWavesPerSimd) void k_mlp_art_w
 
 int launch_ws_f16x3(const void* packed, const float* a0, const float* a1, const float* a2,
                     const float* a3, int64_t B, int S, int act, float* raw, hipStream_t stream) {
-  const int64_t N = B * S;
-  const f4* wsp = static_cast<const f4*>(packed);
-  const float* bias = reinterpret_cast<const float*>(static_cast<const char*>(packed) +
-                                                    NetVanillaFoldH::kStreamBytes);
-  hipLaunchKernelGGL(ws::k_mlp_ws_f16x3, static_cast<int>((N + ws::Geo::kNb - 1) / ws::Geo::kNb),
-                     ws::Geo::kThreads, 0, stream, wsp, bias, a0, a1, a2, a3, B, S, act, raw);
+  static_assert(kRowsOkCovers<ws::Geo>, "mlp_launch's rows_ok covers this grid");
+  hipLaunchKernelGGL(ws::k_mlp_ws_f16x3, chain_grid<ws::Geo>(B * S), ws::Geo::kThreads, 0, stream,
+                     static_cast<const f4*>(packed), stream_bias<NetVanillaFoldH>(packed), a0, a1,
+                     a2, a3, B, S, act, raw);
   return launch_status("aon_mlp_fwd");
 }
 
 int launch_art_ws_f16x3(const void* packed, const float* a0, const float* a1, const float* a2,
                         const float* a3, int64_t B, int S, int act, float* raw, hipStream_t stream) {
-  const int64_t N = B * S;
-  const f4* wsp = static_cast<const f4*>(packed);
-  const float* bias = reinterpret_cast<const float*>(static_cast<const char*>(packed) + NetArtH::kStreamBytes);
-  hipLaunchKernelGGL(ws::k_mlp_art_ws_f16x3, static_cast<int>((N + ws::Geo::kNb - 1) / ws::Geo::kNb),
-                     ws::Geo::kThreads, 0, stream, wsp, bias, a0, a1, a2, a3, B, S, act, raw);
+  static_assert(kRowsOkCovers<ws::Geo>, "art_launch's rows_ok covers this grid");
+  hipLaunchKernelGGL(ws::k_mlp_art_ws_f16x3, chain_grid<ws::Geo>(B * S), ws::Geo::kThreads, 0,
+                     stream, static_cast<const f4*>(packed), stream_bias<NetArtH>(packed), a0, a1,
+                     a2, a3, B, S, act, raw);
   return launch_status("aon_mlp_art_fwd");
 }
 

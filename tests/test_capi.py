@@ -239,3 +239,234 @@ def test_gemm_workspace_bytes_pinned(L):
         if got != row["bytes"]:
             wrong.append((row["name"], got, row["bytes"]))
     assert not wrong, f"(case, bytes, recorded): {wrong}"
+
+
+# ---- every MLP entry point's refusals, message for message -------------------------------------
+# The texts and the order in which checks fire were recorded from the library before the launch /
+# argument-check helpers of the fused MLP files were shared (mlp_layout.hpp check_fwd_args,
+# rows_ok, ...): a call wrong in two ways pins which check comes first.  Every pointer is a fake
+# non-null address (16; 20 = misaligned) and every call is refused, or has N = 0, before any HIP
+# call -- no GPU needed.
+_P, _ODD = ctypes.c_void_p(16), ctypes.c_void_p(20)
+_BIG = 1 << 38  # rows whose 128-row blocks reach 2^31: refused; one block fewer passes the guard
+_TRAIN_MSG = ("AON_PREC_F16X3_TRAIN is the training forward's stream (aon_mlp_fwd_train): render "
+              "with an AON_PREC_F16X3 pack")
+_BF16_MSG = "unsupported precision (AON_PREC_BF16 is the training forward's: aon_mlp_fwd_train_bf16)"
+_FP32_MSG = "AON_PREC_FP32 has no two-pass kernels: render a fp32 pack with aon_mlp_fwd"
+_PR = "packed / raw must be 16-byte aligned"
+_MIXED_FWD = "mixed: 0 fp16x3, 1 trunk bf16, 2 view branch bf16, 3 fp16 weights, 4 fp16 activations"
+_MIXED_PACK = "mixed: 1 trunk bf16, 2 view branch bf16, 3 fp16 weights past the deformation MLP"
+
+
+def _render_cases(fn, inner, own_null, inner_null, prec, B, S, act, packed, raw, two_pass):
+    """Refusals of a render forward whose shared checks run in `inner` (mlp_launch /
+    two_pass_check / art_launch); own_null: pointers the entry point tests itself (first);
+    prec: index of the precision argument or None."""
+    c = [({i: None}, f"{fn}: null pointer") for i in own_null]
+    c += [({i: None}, f"{inner}: null pointer") for i in inner_null]
+    if own_null:
+        c.append(({own_null[0]: None, packed: None}, f"{fn}: null pointer"))
+    c += [({S: 0}, f"{inner}: bad shape"), ({B: -1}, f"{inner}: bad shape"),
+          ({act: 3}, f"{inner}: bad activation"), ({act: -1}, f"{inner}: bad activation"),
+          ({packed: _ODD}, f"{inner}: {_PR}"), ({raw: _ODD}, f"{inner}: {_PR}"),
+          ({B: 0}, None), ({B: _BIG, S: 1}, f"{inner}: too many rows"),
+          ({B: _BIG - 128, S: 1, act: 3}, f"{inner}: bad activation"),
+          ({packed: None, S: 0}, f"{inner}: null pointer"),
+          ({S: 0, act: 3}, f"{inner}: bad shape"),
+          ({act: 3, raw: _ODD}, f"{inner}: bad activation"),
+          ({raw: _ODD, B: _BIG, S: 1}, f"{inner}: {_PR}")]
+    if prec is not None:
+        c += [({prec: 4}, f"{inner}: {_TRAIN_MSG}"), ({prec: 2}, f"{inner}: {_BF16_MSG}"),
+              ({prec: 3}, f"{inner}: {_BF16_MSG}"), ({prec: 99}, f"{inner}: {_BF16_MSG}"),
+              ({prec: 4, packed: None}, f"{inner}: null pointer"),
+              ({prec: 4, S: 0}, f"{inner}: {_TRAIN_MSG}"), ({prec: 2, S: 0}, f"{inner}: {_BF16_MSG}")]
+        if two_pass:
+            c += [({prec: 0}, f"{inner}: {_FP32_MSG}"), ({prec: 0, S: 0}, f"{inner}: {_FP32_MSG}")]
+        else:
+            c += [({prec: 0, B: 0}, None), ({prec: 0, B: _BIG, S: 1}, f"{inner}: too many rows")]
+    return c
+
+
+def _mlp_refusal_table():
+    P = _P
+    t = {}
+    # aon_mlp_fwd(packed, precision, rays_o, rays_d, viewdirs, t, B, S, act, raw, stream)
+    t["aon_mlp_fwd"] = ([P, 1, P, P, P, P, 4, 8, 0, P, None], _render_cases(
+        "aon_mlp_fwd", "mlp_launch", [4, 5], [0, 2, 3, 9], 1, 6, 7, 8, 0, 9, False))
+    # aon_mlp_fwd_encoded(packed, precision, x, condition, B, S, act, raw, stream)
+    t["aon_mlp_fwd_encoded"] = ([P, 1, P, P, 4, 8, 0, P, None], _render_cases(
+        "aon_mlp_fwd_encoded", "mlp_launch", [], [0, 2, 3, 7], 1, 4, 5, 6, 0, 7, False))
+    # aon_mlp_fwd_sigma(packed, precision, rays_o, rays_d, t, B, S, act, raw, stream)
+    t["aon_mlp_fwd_sigma"] = ([P, 1, P, P, P, 4, 8, 0, P, None], _render_cases(
+        "aon_mlp_fwd_sigma", "two_pass_check", [], [0, 2, 3, 4, 8], 1, 5, 6, 7, 0, 8, True))
+    # aon_mlp_fwd_cond(packed, precision, rays_o, rays_d, cond, t, B, S, act, raw, stream)
+    t["aon_mlp_fwd_cond"] = ([P, 1, P, P, P, P, 4, 8, 0, P, None], _render_cases(
+        "aon_mlp_fwd_cond", "two_pass_check", [4], [0, 2, 3, 5, 9], 1, 6, 7, 8, 0, 9, True))
+    # aon_mlp_art_fwd(packed, rays_o, rays_d, viewdirs, t, B, S, act, out, stream)
+    t["aon_mlp_art_fwd"] = ([P, P, P, P, P, 4, 8, 0, P, None], _render_cases(
+        "aon_mlp_art_fwd", "art_launch", [3, 4], [0, 1, 2, 8], None, 5, 6, 7, 0, 8, False))
+    # aon_mlp_art_fwd_points(packed, pos, condition, B, S, act, out, stream)
+    t["aon_mlp_art_fwd_points"] = ([P, P, P, 4, 8, 0, P, None], _render_cases(
+        "aon_mlp_art_fwd_points", "art_launch", [], [0, 1, 2, 6], None, 3, 4, 5, 0, 6, False))
+
+    # aon_mlp_fwd_train(packed, rays_o, rays_d, viewdirs, t, B, S, noise, h, bot, hv, raw, masks,
+    #                   stream): noise may be null
+    f, al = "aon_mlp_fwd_train", "packed / output buffers must be 16-byte aligned"
+    t[f] = ([P, P, P, P, P, 4, 8, None, P, P, P, P, P, None],
+            [({i: None}, f"{f}: null pointer") for i in (0, 1, 2, 3, 4, 8, 9, 10, 11, 12)] +
+            [({12: _ODD}, f"{f}: masks must be 16-byte aligned"), ({6: 0}, f"{f}: bad shape"),
+             ({5: -1}, f"{f}: bad shape")] +
+            [({i: _ODD}, f"{f}: {al}") for i in (0, 8, 9, 10, 11)] +
+            [({5: 0}, None), ({5: _BIG, 6: 1}, f"{f}: too many rows"),
+             ({5: _BIG - 128, 6: 1, 11: _ODD}, f"{f}: {al}"),
+             ({12: _ODD, 6: 0}, f"{f}: masks must be 16-byte aligned"),
+             ({6: 0, 0: _ODD}, f"{f}: bad shape"), ({0: None, 12: _ODD}, f"{f}: null pointer"),
+             ({0: _ODD, 5: _BIG, 6: 1}, f"{f}: {al}")])
+    # aon_mlp_fwd_train_bf16(..., raw, masks, enc, stream): enc may be null
+    f = "aon_mlp_fwd_train_bf16"
+    t[f] = ([P, P, P, P, P, 4, 8, None, P, P, P, P, P, P, None],
+            [({i: None}, f"{f}: null pointer") for i in (0, 1, 2, 3, 4, 8, 9, 10, 11, 12)] +
+            [({6: 0}, f"{f}: bad shape"), ({5: -1}, f"{f}: bad shape")] +
+            [({i: _ODD}, f"{f}: {al}") for i in (0, 8, 9, 10, 11, 12, 13)] +
+            [({5: 0}, None), ({5: 0, 13: None}, None), ({5: _BIG, 6: 1}, f"{f}: too many rows"),
+             ({5: _BIG - 128, 6: 1, 13: _ODD}, f"{f}: {al}"),
+             ({12: _ODD, 6: 0}, f"{f}: bad shape"), ({0: None, 6: 0}, f"{f}: null pointer"),
+             ({0: _ODD, 5: _BIG, 6: 1}, f"{f}: {al}")])
+
+    # aon_mlp_art_fwd_train(packed, rays_o, rays_d, viewdirs, t, B, S, noise, hd, h, bot, hv, enc,
+    #                       xyz, raw, masks, stream); _bf16: ..., masks, enc_bf, mixed, stream
+    a8 = "activation buffers must be 8-byte aligned"
+    for f, tail in (("aon_mlp_art_fwd_train", [None]), ("aon_mlp_art_fwd_train_bf16", [P, 1, None])):
+        c = ([({i: None}, "art_fwd_train: null pointer") for i in (0, 1, 2, 3, 4, 14)] +
+             [({i: None}, "art_fwd_train: null activation buffer") for i in (8, 9, 10, 11, 12, 13, 15)] +
+             [({i: _ODD}, "art_fwd_train: masks / enc must be 16-byte aligned") for i in (12, 15)] +
+             [({6: 0}, "art_fwd_train: bad shape"), ({5: -1}, "art_fwd_train: bad shape"),
+              ({0: _ODD}, f"art_fwd_train: {_PR}"), ({14: _ODD}, f"art_fwd_train: {_PR}")] +
+             [({i: _ODD}, f"art_fwd_train: {a8}") for i in (8, 9, 10, 11)] +
+             [({i: ctypes.c_void_p(24)}, "art_fwd_train: too many rows", {5: _BIG, 6: 1})
+              for i in (8, 9, 10, 11)] +
+             [({5: 0}, None), ({5: _BIG, 6: 1}, "art_fwd_train: too many rows"),
+              ({5: _BIG - 128, 6: 1, 8: _ODD}, f"art_fwd_train: {a8}"),
+              ({0: None, 8: None}, "art_fwd_train: null pointer"),
+              ({8: None, 12: _ODD}, "art_fwd_train: null activation buffer"),
+              ({12: _ODD, 6: 0}, "art_fwd_train: masks / enc must be 16-byte aligned"),
+              ({6: 0, 0: _ODD}, "art_fwd_train: bad shape"),
+              ({0: _ODD, 8: _ODD}, f"art_fwd_train: {_PR}"),
+              ({8: _ODD, 5: _BIG, 6: 1}, f"art_fwd_train: {a8}")])
+        if len(tail) == 3:
+            eb = "art_fwd_train: enc_bf: a 16-byte aligned buffer"
+            c += [({17: 5}, f"{f}: {_MIXED_FWD}"), ({17: -1}, f"{f}: {_MIXED_FWD}"),
+                  ({17: 5, 0: None}, f"{f}: {_MIXED_FWD}"),
+                  ({16: None}, eb), ({16: _ODD}, eb), ({16: None, 17: 0}, eb),
+                  ({16: None, 12: _ODD}, "art_fwd_train: masks / enc must be 16-byte aligned"),
+                  ({16: None, 6: 0}, eb)]
+            c += [({17: m, 5: 0}, None) for m in range(5)]
+            c += [({17: m, 5: _BIG, 6: 1}, "art_fwd_train: too many rows") for m in range(5)]
+        t[f] = ([P, P, P, P, P, 4, 8, None, P, P, P, P, P, P, P, P] + tail, c)
+
+    # aon_mlp_bwd(packed, draw, masks, N, dzv, dzb, dz, work, stream) and its bf16 twin (whose
+    # 256-row blocks move the row guard to 2^39)
+    al = "buffers must be 16-byte aligned"
+    for f, big, rpb in (("aon_mlp_bwd", _BIG, 128), ("aon_mlp_bwd_bf16", 2 * _BIG, 256)):
+        t[f] = ([P, P, P, 5, P, P, P, P, None],
+                [({i: None}, "bwd_launch: null pointer") for i in (0, 1, 2, 4, 5, 6, 7)] +
+                [({3: -1}, "bwd_launch: bad shape")] +
+                [({i: _ODD}, f"bwd_launch: {al}") for i in (0, 1, 2, 4, 5, 6)] +
+                [({3: 0}, None), ({3: 0, 7: _ODD}, None), ({3: big}, "bwd_launch: too many rows"),
+                 ({3: big - rpb, 6: _ODD}, f"bwd_launch: {al}"),
+                 ({0: None, 3: -1}, "bwd_launch: null pointer"),
+                 ({3: -1, 0: _ODD}, "bwd_launch: bad shape"),
+                 ({0: _ODD, 3: big}, f"bwd_launch: {al}")])
+    # aon_mlp_art_bwd(packed, draw, masks, enc, N, dzv, dbot, dz, dxp, dzd, work, stream)
+    for f, big, rpb in (("aon_mlp_art_bwd", _BIG, 128), ("aon_mlp_art_bwd_bf16", 2 * _BIG, 256)):
+        t[f] = ([P, P, P, P, 5, P, P, P, P, P, P, None],
+                [({i: None}, "art_bwd: null pointer") for i in (0, 1, 2, 3, 5, 6, 7, 8, 9, 10)] +
+                [({4: -1}, "art_bwd: bad shape")] +
+                [({i: _ODD}, f"art_bwd: {al}") for i in (0, 1, 2, 3, 5, 6, 7, 9)] +
+                [({4: 0}, None), ({4: 0, 8: _ODD}, None), ({4: big}, "art_bwd: too many rows"),
+                 ({4: big - rpb, 9: _ODD}, f"art_bwd: {al}"),
+                 ({0: None, 4: -1}, "art_bwd: null pointer"),
+                 ({4: -1, 0: _ODD}, "art_bwd: bad shape"),
+                 ({0: _ODD, 4: big}, f"art_bwd: {al}")])
+    return t
+
+
+_MLP_REFUSALS = _mlp_refusal_table()
+
+
+def _run_cases(L, fn, base, cases):
+    lib, wrong = L.lib(), []
+    for case in cases:
+        args = list(base)
+        for d in case[2:] + (case[0],):
+            for i, v in d.items():
+                args[i] = v
+        st = getattr(lib, fn)(*args)
+        msg = lib.aon_last_error().decode() if st else None
+        if (st, msg) != ((-1, case[1]) if case[1] is not None else (0, None)):
+            wrong.append((case[0], st, msg, case[1]))
+    assert not wrong, f"{fn} (overrides, status, message, expected): {wrong}"
+
+
+@pytest.mark.parametrize("fn", sorted(_MLP_REFUSALS))
+def test_mlp_entry_point_refusals(L, fn):
+    base, cases = _MLP_REFUSALS[fn]
+    assert len(cases) >= 12
+    _run_cases(L, fn, base, cases)
+
+
+def test_mlp_pack_refusals(L):
+    """The same for the seven pack entry points: null / misaligned buffers, a refused precision or
+    `mixed`, a null layer pointer -- each with well-shaped parameter tables, so only the check
+    under test stands between the call and a launch."""
+    P = _P
+    al = "packed buffer must be 16-byte aligned"
+
+    def vanilla(**null):
+        prm = _struct_with(L, L.AonMlpParams, 12, L.MLP_SHAPES)
+        for k in null:
+            setattr(prm, k, None)
+        return ctypes.byref(prm)
+
+    def art(**null):
+        prm = _struct_with(L, L.AonMlpArtParams, 20, L.ART_SHAPES)
+        for k in null:
+            setattr(prm, k, None)
+        return ctypes.byref(prm)
+
+    f = "aon_mlp_pack"
+    _run_cases(L, f, [vanilla(), 1, P, None], [
+        ({0: None}, f"{f}: null pointer"), ({2: None}, f"{f}: null pointer"),
+        ({1: 3}, f"{f}: unsupported precision"), ({1: -1}, f"{f}: unsupported precision"),
+        ({2: _ODD}, f"{f}: {al}"), ({1: 3, 2: None}, f"{f}: null pointer"),
+        ({1: 3, 2: _ODD}, f"{f}: unsupported precision"),
+        ({0: vanilla(density_w=None)}, f"{f}: null layer parameter"),
+        ({0: vanilla(rgb_b=None), 1: 0}, f"{f}: null layer parameter"),
+        ({0: vanilla(rgb_b=None), 2: _ODD}, f"{f}: {al}")])
+    for f in ("aon_mlp_bwd_pack", "aon_mlp_bwd_pack_bf16"):
+        _run_cases(L, f, [vanilla(), P, None], [
+            ({0: None}, "bwd_pack: null pointer"), ({1: None}, "bwd_pack: null pointer"),
+            ({1: _ODD}, f"bwd_pack: {al}"),
+            ({0: vanilla(rgb_w=None)}, "bwd_pack: null layer weight"),
+            ({0: vanilla(density_w=None)}, "bwd_pack: null layer weight"),
+            ({0: vanilla(density_w=None), 1: _ODD}, f"bwd_pack: {al}")])
+    for f in ("aon_mlp_art_pack", "aon_mlp_art_pack_bf16"):
+        _run_cases(L, f, [art(), P, None], [
+            ({0: None}, "art_pack: null pointer"), ({1: None}, "art_pack: null pointer"),
+            ({1: _ODD}, f"art_pack: {al}"),
+            ({0: art(deformation_b=None)}, "art_pack: null layer parameter"),
+            ({0: art(rgb_w=None), 1: _ODD}, f"art_pack: {al}")])
+    f = "aon_mlp_art_pack_mixed"
+    _run_cases(L, f, [art(), 1, P, None], [
+        ({1: 0}, f"{f}: {_MIXED_PACK}"), ({1: 4}, f"{f}: {_MIXED_PACK}"),
+        ({1: 4, 0: None}, f"{f}: {_MIXED_PACK}"),
+        ({0: None}, "art_pack: null pointer"), ({1: 3, 2: None}, "art_pack: null pointer"),
+        ({1: 2, 2: _ODD}, f"art_pack: {al}"),
+        ({1: 3, 0: art(density_w=None)}, "art_pack: null layer parameter")])
+    for f in ("aon_mlp_art_bwd_pack", "aon_mlp_art_bwd_pack_bf16"):
+        _run_cases(L, f, [art(), P, None], [
+            ({0: None}, "art_bwd_pack: null pointer"), ({1: None}, "art_bwd_pack: null pointer"),
+            ({1: _ODD}, f"art_bwd_pack: {al}"),
+            ({0: art(deformation_w=None)}, "art_bwd_pack: null layer weight"),
+            ({0: art(density_w=None)}, "art_bwd_pack: null layer weight"),
+            ({0: art(density_w=None), 1: _ODD}, f"art_bwd_pack: {al}")])

@@ -1,13 +1,15 @@
-"""What the vanilla and the articulated render level share (train.py / train_art.py, model.py /
-model_autodecoder.py), once: the event timers; the cache of packed weight streams, whose
+"""What the vanilla and the articulated render level share (train.py / train_art.py,
+model_autodecoder.py, and two_level.py, the coarse/fine driver of both models, which holds what
+happens above a level), once: the event timers; the cache of packed weight streams, whose
 namespace ("train", "train_art") is also the name the fp16x3 range guard keeps a pack under;
 the compositor calls with their allocations; the weight gradients dW = dZ^T X of the fused
 backward chains' kept tensors, each operand an ``Operand`` record that dweight_kwargs turns into
 aon_gemm's layout / scale / kernel-licence keywords; the all-GEMM backward products; and the
 articulated network layer by layer -- Geo, the latent folds, and art_forward, the one walker
 over its layers (training keeps one tensor per layer, inference alternates two buffers per
-width: LayerBuffers).  Callers launch what they launched before they shared this: same entry
-points, arguments, order and allocations."""
+width: LayerBuffers).  Callers launch what they launched before they shared this, and so does
+two_level.py above them: same entry points, arguments, order and allocations (there also the
+same random draws in the same order)."""
 import collections
 
 import torch

@@ -20,15 +20,15 @@ aonerf/numerics.py), ``fused_march`` and ``range_check`` are attributes of each 
 Intermediates live in HBM (a 640x480 frame needs ~1.6 GB), so a whole frame is one launch
 per stage instead of the reference's 80 chunk iterations.
 """
-import warnings
+from types import SimpleNamespace
 
 import torch
 import torch.nn as nn
 import torch.nn.init as init
 
 from . import _lib as L
-from . import helper
-from .level import composite_fwd, events as _events, record as _record
+from . import helper, two_level
+from .two_level import composite_march, fine_uniforms, level_t_vals, march_ok  # noqa: F401 (re-exported)
 from .numerics import resolve as _resolve_numerics
 
 _DEFAULT_GEOMETRY = dict(min_deg_point=0, max_deg_point=10, deg_view=4, netdepth=8, netwidth=256,
@@ -153,60 +153,6 @@ class NeRFMLP(nn.Module):
         return raw[..., :3], raw[..., 3:]
 
 
-def fine_uniforms(B, num_fine_samples, randomized, dev, u_fine=None):
-    """The u of the fine level's inverse-CDF sampling (helper.py:227-231) and its row stride:
-    per-ray draws in randomized mode (or the injected ``u_fine``), else one shared linspace."""
-    if randomized:
-        u = torch.rand((B, num_fine_samples), device=dev) if u_fine is None else L.contig(u_fine)
-        return u, num_fine_samples
-    return helper.eval_u(num_fine_samples, dev), 0
-
-
-def composite_march(raw, t_vals, d, white_bkgd, act, u, u_stride, num_fine_samples,
-                    keep_weights):
-    """Coarse compositing + the fine level's resampling in one kernel (aon_composite_march):
-    (comp, acc, depth, weights or None), t_fine (B, S + Nf) -- helper.py:157-252 and
-    model.py:163-172, the coarse weights kept on chip unless asked for."""
-    B, S = t_vals.shape
-    dev = t_vals.device
-    comp = torch.empty((B, 3), device=dev)
-    acc = torch.empty((B,), device=dev)
-    depth = torch.empty((B,), device=dev)
-    weights = torch.empty((B, S), device=dev) if keep_weights else None
-    t_fine = torch.empty((B, S + num_fine_samples), device=dev)
-    L.call("aon_composite_march", L.ptr(raw), L.ptr(t_vals), L.ptr(d), B, S, int(bool(white_bkgd)),
-           act, L.ptr(u), u_stride, num_fine_samples, L.ptr(comp), L.ptr(acc), L.ptr(weights),
-           L.ptr(depth), L.ptr(t_fine), L.stream(dev))
-    return (comp, acc, depth, weights), t_fine
-
-
-def march_ok(S, num_fine_samples, fused=True):
-    """The fused march kernel's limits (include/aonerf.h: 3 <= S <= 256, 1 <= Ns <= 256); larger
-    N_importance (up to aon_sample_pdf's 512) takes the two-kernel path, as does a model whose
-    ``fused_march`` is False (aon_composite_fwd + aon_sample_pdf, bit-identical outputs)."""
-    return fused and 3 <= S <= 256 and 1 <= num_fine_samples <= 256
-
-
-def level_t_vals(level, o, d, t_prev, w_prev, randomized, near, far, num_coarse_samples,
-                 num_fine_samples, lindisp, u_coarse=None, u_fine=None):
-    """Sample positions of a level: stratified (helper.py:106-133) or inverse-CDF resampling
-    of the previous level's weights merged with its samples (model.py:163-172)."""
-    dev = o.device
-    B = o.shape[0]
-    if level == 0:
-        t_vals, _ = helper.sample_along_rays(o, d, num_coarse_samples, near, far, randomized,
-                                             lindisp, u=u_coarse, want_coords=False)
-        return t_vals
-    Sc = t_prev.shape[1]
-    u, u_stride = fine_uniforms(B, num_fine_samples, randomized, dev, u_fine)
-    w_prev = L.contig(w_prev.detach())
-    t_new = torch.empty((B, Sc + num_fine_samples), device=dev)
-    # bins = mids of t (model.py:163), weights[..., 1:-1] as a strided view
-    L.call("aon_sample_pdf", None, 0, L.ptr(w_prev[:, 1:]), Sc, B, Sc - 1, num_fine_samples,
-           L.ptr(u), u_stride, L.ptr(t_prev), Sc, None, None, L.ptr(t_new), None, L.stream(dev))
-    return t_new
-
-
 class NeRF(nn.Module):
     """reference model.py:123-199 (two-level coarse/fine render)."""
 
@@ -261,126 +207,58 @@ class NeRF(nn.Module):
         With autograd enabled and trainable parameters, each level runs the training path
         (train.RenderLevel: the fused training forward aon_mlp_fwd_train, which also stores the
         activations and their ReLU' bits, then the HIP backward); otherwise the fused inference
-        kernels.
+        kernels (two_level.py drives the two levels either way).
         """
         o, d, v = rays["rays_o"], rays["rays_d"], rays["viewdirs"]
         L.require_gpu(o, d, v)
         o, d, v = L.contig(o), L.contig(d), L.contig(v)
-        training = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
-        B = o.shape[0]
-        dev = o.device
-        fine_only = bool(fine_only) and not (training or return_weights or return_intermediates)
-        two_pass = fine_only and self.coarse_mlp.precision == self.fine_mlp.precision == "f16x3"
-        cond = helper.pos_enc(v, 0, self.deg_view) if two_pass else None
-        # the fp16x3 overflow fallback below re-renders with the same random draws (density
-        # noise, stratified t, fine u) and leaves the generator where one forward leaves it
-        rng = torch.cuda.get_rng_state(dev) if randomized and not training else None
-        ret = []
-        t_vals = weights = t_next = None
-        token, joined = None, {}
+        kw = dict(u_coarse=u_coarse, u_fine=u_fine, return_weights=return_weights,
+                  return_intermediates=return_intermediates, timers=timers)
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            spec = SimpleNamespace(model=self, train_level=self._train_level(timers))
+            return two_level.train(spec, o, d, v, randomized, white_bkgd, near, far, **kw)
+        fine_only = bool(fine_only) and not (return_weights or return_intermediates)
+        return two_level.render(self._render_spec(v, fine_only), o, d, v, randomized, white_bkgd,
+                                near, far, fine_only=fine_only, **kw)
+
+    def _train_level(self, timers):
+        from . import train
         cfg = self.train_numerics
-        if training:
-            from . import train
-            if cfg.overlap_dweight and cfg.fused_backward and timers is None:
-                # both levels' parameters through one Join: its backward, after both levels',
-                # joins the fine level's weight-gradient stream (overlap_dweight)
-                token = train.JoinToken()
-                ps = [p for m in (self.coarse_mlp, self.fine_mlp) for l in m._layers()
-                      for p in (l.weight, l.bias)]
-                joined = dict(zip(map(id, ps), train.Join.apply(token, *ps)))
-        for level in range(2):
-            with torch.no_grad():
-                t_vals = t_next if t_next is not None else self._level_t(
-                    level, o, d, t_vals, weights, randomized, near, far, u_coarse, u_fine)
-            mlp = self.coarse_mlp if level == 0 else self.fine_mlp
-            S = t_vals.shape[1]
-            if training:
-                from .train import RenderLevel
-                noise = None
-                if self.noise_std > 0 and randomized:  # model.py:183-184
-                    noise = torch.rand((B * S,), device=dev) * self.noise_std
-                params = [p for m in mlp._layers() for p in (m.weight, m.bias)]
-                params = [joined.get(id(p), p) for p in params]
-                comp, acc, depth, weights = RenderLevel.apply(o, d, v, t_vals, bool(white_bkgd),
-                                                              noise, token, cfg, timers, *params)
-                out = (comp, acc, depth, weights) if return_weights else (comp, acc, depth)
-                if return_intermediates:
-                    out = out + (dict(t_vals=t_vals, weights=weights),)
-                ret.append(out)
-                continue
-            # the last level's weights are an output only when asked for: otherwise the
-            # compositor skips writing them (4 B of its 24 B per sample)
-            keep_w = level == 0 or return_weights or return_intermediates
-            march = level == 0 and march_ok(S, self.num_fine_samples, self.fused_march)
-            if march:  # the coarse weights are needed on chip only
-                keep_w = return_weights or return_intermediates
-            with torch.no_grad():
-                out, weights, t_next = self._render_level_fused(
-                    mlp, o, d, v, t_vals, randomized, white_bkgd, level, timers, keep_w,
-                    sigma_only=two_pass and level == 0, cond=cond if level == 1 else None,
-                    # drawn inside, after the level's density noise (the reference's RNG order)
-                    march_u=(lambda: fine_uniforms(B, self.num_fine_samples, randomized, dev,
-                                                   u_fine)) if march else None)
-            if not return_weights:
-                out = out[:3] + out[4:]
-            if not return_intermediates:
-                out = out[:4] if return_weights else out[:3]
-            ret.append(None if fine_only and level == 0 else out)
-        if (not training and self.range_check and self.coarse_mlp.precision.startswith("f16x3")
-                and not torch.cuda.is_current_stream_capturing()
-                and L.range_overflow([self.coarse_mlp._packed, self.fine_mlp._packed])):
-            # an activation left the fp16x3 split's range (|x| > 8188): these outputs are
-            # invalid -- render again on the exact-fp32 MFMA kernels (no range limit)
-            warnings.warn("NeRF: an MLP activation exceeded the fp16x3 range; re-rendered with "
-                          "precision='fp32'", RuntimeWarning)
-            prec = self.coarse_mlp.precision
-            self.set_precision("fp32")
-            if rng is not None:
-                torch.cuda.set_rng_state(rng, dev)
-            try:
-                return self.forward(rays, randomized, white_bkgd, near, far, u_coarse=u_coarse,
-                                    u_fine=u_fine, return_weights=return_weights,
-                                    return_intermediates=return_intermediates, timers=timers,
-                                    fine_only=fine_only)
-            finally:
-                self.set_precision(prec)
-        return ret
+        token, joined = None, {}
+        if cfg.overlap_dweight and cfg.fused_backward and timers is None:
+            # both levels' parameters through one Join: its backward, after both levels',
+            # joins the fine level's weight-gradient stream (overlap_dweight)
+            token = train.JoinToken()
+            ps = [p for m in (self.coarse_mlp, self.fine_mlp) for l in m._layers()
+                  for p in (l.weight, l.bias)]
+            joined = dict(zip(map(id, ps), train.Join.apply(token, *ps)))
 
-    def _level_t(self, level, o, d, t_prev, w_prev, randomized, near, far, u_coarse, u_fine):
-        return level_t_vals(level, o, d, t_prev, w_prev, randomized, near, far,
-                            self.num_coarse_samples, self.num_fine_samples, self.lindisp,
-                            u_coarse, u_fine)
+        def train_level(level, mlp, o, d, v, t_vals, white_bkgd, noise, timers):
+            params = [joined.get(id(p), p) for m in mlp._layers() for p in (m.weight, m.bias)]
+            return train.RenderLevel.apply(o, d, v, t_vals, bool(white_bkgd), noise, token, cfg,
+                                           timers, *params)
+        return train_level
 
-    def _render_level_fused(self, mlp, o, d, v, t_vals, randomized, white_bkgd, level, timers,
-                            keep_weights=True, march_u=None, sigma_only=False, cond=None):
-        """One inference level: fused MLP, then compositing -- with ``march_u`` (a callable
-        returning the fine level's (u, u_stride)) also the next level's resampling in the same
-        kernel (returned t_next, else None).  ``sigma_only``: the density-only MLP pass (the
-        level's colour comes out as the compositor's of a zero rgb: only its weights and t_next
-        mean anything); ``cond``: the per-ray view encodings (forward_rays)."""
-        B, S = t_vals.shape
-        dev = o.device
-        # the activations (model.py:186-187) run in the MLP epilogue, unless density noise
-        # must be added to the raw sigma first (model.py:183-184)
-        noisy = self.noise_std > 0 and randomized
-        ev = _events(timers)
-        act = L.ACT_NONE if noisy else L.ACT_VANILLA
-        if sigma_only:
-            raw = mlp.forward_sigma(o, d, t_vals, act=act)
-        else:
-            raw = mlp.forward_rays(o, d, v, t_vals, act=act, cond=cond)
-        _record(timers, ev, f"mlp{level}", B * S)
-        if noisy:
-            raw[:, 3] += torch.rand_like(raw[:, 3]) * self.noise_std
-        act = L.ACT_VANILLA if noisy else L.ACT_NONE
-        t_next = None
-        ev = _events(timers)
-        if march_u is not None:
-            u, u_stride = march_u()
-            (comp, acc, depth, weights), t_next = composite_march(
-                raw, t_vals, d, white_bkgd, act, u, u_stride, self.num_fine_samples, keep_weights)
-            _record(timers, ev, f"march{level}", B * S)
-        else:
-            comp, acc, depth, weights = composite_fwd(raw, t_vals, d, white_bkgd, act, keep_weights)
-            _record(timers, ev, f"comp{level}", B * S)
-        return (comp, acc, depth, weights, dict(t_vals=t_vals, weights=weights, rgb_sigma=raw)), weights, t_next
+    def _render_spec(self, v, fine_only):
+        mlps = (self.coarse_mlp, self.fine_mlp)
+        two_pass = fine_only and mlps[0].precision == mlps[1].precision == "f16x3"
+        cond = helper.pos_enc(v, 0, self.deg_view) if two_pass else None  # once per forward
+
+        def mlp_raw(level, mlp, o, d, v, t_vals, act):
+            if not (two_pass and mlp.precision == "f16x3"):  # (the fallback's fp32: aon_mlp_fwd)
+                return mlp.forward_rays(o, d, v, t_vals, act=act)
+            if level == 0:  # density only: the compositor's colour of a zero rgb means nothing
+                return mlp.forward_sigma(o, d, t_vals, act=act)
+            return mlp.forward_rays(o, d, v, t_vals, act=act, cond=cond)
+
+        return SimpleNamespace(
+            model=self, mlp_raw=mlp_raw, keep_fine_weights=False, extras_key="rgb_sigma",
+            # the activations (model.py:186-187) run in the MLP epilogue, unless density noise
+            # must be added to the raw sigma first (model.py:183-184)
+            acts=lambda noisy: (L.ACT_NONE, L.ACT_VANILLA) if noisy else (L.ACT_VANILLA, L.ACT_NONE),
+            range_checked=lambda: self.range_check and mlps[0].precision.startswith("f16x3"),
+            packs=lambda: [m._packed for m in mlps],
+            # (past |x| = 8188 the fp16x3 split cannot hold an activation; fp32 has no limit)
+            fallback=lambda: two_level.switched(mlps, "precision", "fp32"),
+            warning="NeRF: an MLP activation exceeded the fp16x3 range; re-rendered with "
+                    "precision='fp32'")

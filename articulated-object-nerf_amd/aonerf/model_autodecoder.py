@@ -22,7 +22,7 @@ latent, one tiny GEMM each).  ``NeRFMLP.fused = False`` selects the layer-by-lay
 (level.art_forward, the walker the training path shares), every product on the f16x3 MFMA GEMM
 (aon_gemm): also the fallback when an activation leaves the fused kernel's fp16x3 range.
 """
-import warnings
+from types import SimpleNamespace
 
 import torch
 import torch.nn as nn
@@ -30,7 +30,7 @@ import torch.nn.init as init
 
 from . import _lib as L
 from . import level as _level
-from .model import _events, _record, composite_march, fine_uniforms, level_t_vals, march_ok
+from . import two_level
 from .numerics import resolve as _resolve_numerics
 
 
@@ -226,99 +226,37 @@ class NeRF_AE_Art(nn.Module):  # noqa: N801 (reference name)
         With autograd enabled and trainable parameters or latent codes, each level runs the
         training path (train_art.ArtRenderLevel: the fused training forward
         aon_mlp_art_fwd_train, which also stores the activations, then the HIP backward into the
-        MLP parameters and the latent codes); otherwise the fused inference kernel."""
+        MLP parameters and the latent codes); otherwise the fused inference kernel (two_level.py
+        drives the two levels either way)."""
         o, d, v = rays["rays_o"], rays["rays_d"], rays["viewdirs"]
         L.require_gpu(o, d, v)
         o, d, v = L.contig(o), L.contig(d), L.contig(v)
         training = torch.is_grad_enabled() and (
             any(p.requires_grad for p in self.parameters())
             or any(x.requires_grad for x in latents.values()))
-        if training:
-            return self._forward_train(o, d, v, randomized, white_bkgd, near, far, latents,
-                                       u_coarse, u_fine, return_weights, return_intermediates,
-                                       timers)
-        with torch.no_grad():
-            return self._forward_render(o, d, v, randomized, white_bkgd, near, far, latents,
-                                        u_coarse, u_fine, return_weights, return_intermediates,
-                                        timers)
+        run = two_level.train if training else two_level.render
+        return run(self._spec(latents), o, d, v, randomized, white_bkgd, near, far,
+                   u_coarse=u_coarse, u_fine=u_fine, return_weights=return_weights,
+                   return_intermediates=return_intermediates, timers=timers)
 
-    def _forward_train(self, o, d, v, randomized, white_bkgd, near, far, latents, u_coarse,
-                       u_fine, return_weights, return_intermediates, timers=None):
-        from .train_art import render_level
-
-        B, dev = o.shape[0], o.device
-        ret = []
-        t_vals = weights = None
-        for level in range(2):
-            with torch.no_grad():  # no gradient reaches the sampling (helper.py:246-252)
-                t_vals = level_t_vals(level, o, d, t_vals, weights, randomized, near, far,
-                                      self.num_coarse_samples, self.num_fine_samples,
-                                      self.lindisp, u_coarse, u_fine)
-            mlp = self.coarse_mlp if level == 0 else self.fine_mlp
-            noise = None
-            if self.noise_std > 0 and randomized:  # model_autodecoder.py:318-319
-                noise = torch.rand((B * t_vals.shape[1],), device=dev) * self.noise_std
-            comp, acc, depth, weights = render_level(mlp, o, d, v, t_vals, white_bkgd, latents,
-                                                     noise, self.train_numerics, timers)
-            out = (comp, acc, depth, weights) if return_weights else (comp, acc, depth)
-            if return_intermediates:
-                out = out + (dict(t_vals=t_vals, weights=weights),)
-            ret.append(out)
-        return ret
-
-    def _forward_render(self, o, d, v, randomized, white_bkgd, near, far, latents, u_coarse,
-                        u_fine, return_weights, return_intermediates, timers=None):
-        B, dev = o.shape[0], o.device
-        # the overflow fallback below re-renders with the same random draws
-        rng = torch.cuda.get_rng_state(dev) if randomized else None
-        ret = []
-        t_vals = weights = t_next = None
-        for level in range(2):
-            t_vals = t_next if t_next is not None else level_t_vals(
-                level, o, d, t_vals, weights, randomized, near, far, self.num_coarse_samples,
-                self.num_fine_samples, self.lindisp, u_coarse, u_fine)
-            mlp = self.coarse_mlp if level == 0 else self.fine_mlp
-            S = t_vals.shape[1]
-            ev = _events(timers)
-            raw = mlp.forward_rays(o, d, v, t_vals, latents)
-            _record(timers, ev, f"mlp{level}", B * S)
-            if self.noise_std > 0 and randomized:  # model_autodecoder.py:318-319
-                raw[:, 3].copy_(raw[:, 3] + torch.rand_like(raw[:, 3]) * self.noise_std)
-            ev = _events(timers)
-            if level == 0 and march_ok(S, self.num_fine_samples, self.fused_march):
-                # coarse compositing + the fine level's resampling in one kernel; the coarse
-                # weights reach HBM only when asked for
-                u, u_stride = fine_uniforms(B, self.num_fine_samples, randomized, dev, u_fine)
-                (comp, acc, depth, weights), t_next = composite_march(
-                    raw, t_vals, d, white_bkgd, L.ACT_ARTIC, u, u_stride, self.num_fine_samples,
-                    return_weights or return_intermediates)
-                _record(timers, ev, f"march{level}", B * S)
-            else:
-                comp, acc, depth, weights = _level.composite_fwd(raw, t_vals, d, white_bkgd,
-                                                                L.ACT_ARTIC)
-                _record(timers, ev, f"comp{level}", B * S)
-            out = (comp, acc, depth, weights) if return_weights else (comp, acc, depth)
-            if return_intermediates:
-                out = out + (dict(t_vals=t_vals, weights=weights, raw=raw),)
-            ret.append(out)
+    def _spec(self, latents):
         mlps = (self.coarse_mlp, self.fine_mlp)
-        if (self.range_check and all(m._fused_ok() for m in mlps)
-                and not torch.cuda.is_current_stream_capturing()
-                and L.range_overflow([getattr(m, "_art_packed", None) for m in mlps])):
-            # an activation left the fp16x3 split's range (|x| > 8188) in the fused kernel:
-            # render again layer by layer (aon_gemm operands carry 2^-8: range 1.6e7)
-            warnings.warn("NeRF_AE_Art: an MLP activation exceeded the fused fp16x3 range; "
-                          "re-rendered on the layer-by-layer path", RuntimeWarning)
-            fused = [m.fused for m in mlps]
-            for m in mlps:
-                m.fused = False
-            if rng is not None:
-                torch.cuda.set_rng_state(rng, dev)
-            try:
-                return self._forward_render(o, d, v, randomized, white_bkgd, near, far, latents,
-                                            u_coarse, u_fine, return_weights,
-                                            return_intermediates, timers)
-            finally:
-                for m, f in zip(mlps, fused):
-                    m.fused = f
-        return ret
+
+        def train_level(level, mlp, o, d, v, t_vals, white_bkgd, noise, timers):
+            from .train_art import render_level
+            return render_level(mlp, o, d, v, t_vals, white_bkgd, latents, noise,
+                                self.train_numerics, timers)
+
+        return SimpleNamespace(
+            model=self, train_level=train_level,
+            mlp_raw=lambda level, mlp, o, d, v, t_vals, act: mlp.forward_rays(
+                o, d, v, t_vals, latents, act=act),
+            # model_autodecoder.py:321-323 always in the compositor (AON_ACT_ARTIC)
+            acts=lambda noisy: (L.ACT_NONE, L.ACT_ARTIC),
+            keep_fine_weights=True, extras_key="raw",
+            range_checked=lambda: self.range_check and all(m._fused_ok() for m in mlps),
+            packs=lambda: [getattr(m, "_art_packed", None) for m in mlps],
+            # (the layer-by-layer path's aon_gemm operands carry 2^-8: range 1.6e7, not 8188)
+            fallback=lambda: two_level.switched(mlps, "fused", False),
+            warning="NeRF_AE_Art: an MLP activation exceeded the fused fp16x3 range; "
+                    "re-rendered on the layer-by-layer path")

@@ -238,6 +238,9 @@ _SIGNATURES = {
                               ctypes.c_double, ctypes.c_double, ctypes.c_double, c_i64, vp]),
     "aon_pos_enc_bwd": (c_int, [vp, c_i64, vp, c_i64, c_i64, c_int, c_int, c_int, vp, c_i64, vp]),
     "aon_latent_reg": (c_int, [vp, c_i64, c_i64, c_float, c_int, vp, vp, vp]),
+    "aon_art_latent_grad_workspace_bytes": (c_size, [c_i64]),
+    "aon_art_latent_grad": (c_int, [ctypes.POINTER(AonMlpArtParams), vp, vp, vp, vp, c_int, c_i64,
+                                    vp, vp, vp, vp, vp]),
 }
 
 _lib = None

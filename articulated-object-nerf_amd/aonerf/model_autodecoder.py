@@ -218,7 +218,7 @@ class NeRF_AE_Art(nn.Module):  # noqa: N801 (reference name)
 
     def forward(self, rays, randomized, white_bkgd, near, far, latents, train=True, *,
                 u_coarse=None, u_fine=None, return_weights=False, return_intermediates=False,
-                timers=None):
+                timers=None, latent_only=False):
         """reference model_autodecoder.py:278-337 -> [(comp_rgb, acc, depth)_coarse, (...)_fine]
         (``u_coarse`` / ``u_fine`` inject randomized-mode uniforms; the extras as NeRF.forward;
         ``timers`` (dict) records hip events around each level's MLP / composite launches).
@@ -227,7 +227,8 @@ class NeRF_AE_Art(nn.Module):  # noqa: N801 (reference name)
         training path (train_art.ArtRenderLevel: the fused training forward
         aon_mlp_art_fwd_train, which also stores the activations, then the HIP backward into the
         MLP parameters and the latent codes); otherwise the fused inference kernel (two_level.py
-        drives the two levels either way)."""
+        drives the two levels either way).  ``latent_only`` (the training path only): gradients
+        for the latent codes alone, the MLPs frozen (train_art.render_level; latent_fit.py)."""
         o, d, v = rays["rays_o"], rays["rays_d"], rays["viewdirs"]
         L.require_gpu(o, d, v)
         o, d, v = L.contig(o), L.contig(d), L.contig(v)
@@ -235,17 +236,17 @@ class NeRF_AE_Art(nn.Module):  # noqa: N801 (reference name)
             any(p.requires_grad for p in self.parameters())
             or any(x.requires_grad for x in latents.values()))
         run = two_level.train if training else two_level.render
-        return run(self._spec(latents), o, d, v, randomized, white_bkgd, near, far,
+        return run(self._spec(latents, latent_only), o, d, v, randomized, white_bkgd, near, far,
                    u_coarse=u_coarse, u_fine=u_fine, return_weights=return_weights,
                    return_intermediates=return_intermediates, timers=timers)
 
-    def _spec(self, latents):
+    def _spec(self, latents, latent_only=False):
         mlps = (self.coarse_mlp, self.fine_mlp)
 
         def train_level(level, mlp, o, d, v, t_vals, white_bkgd, noise, timers):
             from .train_art import render_level
             return render_level(mlp, o, d, v, t_vals, white_bkgd, latents, noise,
-                                self.train_numerics, timers)
+                                self.train_numerics, timers, latent_only)
 
         return SimpleNamespace(
             model=self, train_level=train_level,

@@ -18,6 +18,8 @@ gradients for the level's 40 MLP parameters AND the three latent codes:
             pos_enc(x') (skip + first layer) through pos_enc's backward into the deformation
             head and MLP -> per layer dW = dZ^T X with db = sum_rows dZ from the same pass
             (aon_gemm); or the whole chain as GEMMs + aon_pos_enc_bwd (fused_backward False).
+            latent_only (the MLPs frozen, latent_fit.py): the chain, then the three code
+            gradients from four of its tensors in one call (aon_art_latent_grad), no dW.
 
 The latent codes are the same row for every sample (repeated over B*S rows,
 model_autodecoder.py:186-194), so their columns are folded into per-call biases in the
@@ -256,6 +258,48 @@ def _backward_level(geo, P, G, lat, dlat, xyz, enc, venc, S, hd, h, bot, hv, dra
     dlatent(DEF0, 3 + geo.n_shape, art, dart, False)
 
 
+def _chain(geo, P, enc, S, draw, masks, bf16, timers=None):
+    """The fused backward chain of one level (aon_mlp_art_bwd[_bf16]) from dL/d raw (R, 4) ->
+    (dzv, dbot, dz, dxp, dzd, work): every layer's dL/d pre-activation, tiled (dxp row-major), and
+    the word with the chain's per-call gradient scale.  ``enc``: the forward's pos_enc(x'), tiled
+    or row-major (R, 63)."""
+    R, dev = draw.shape[0], draw.device
+    NR = tiles.rows(R)
+    dt = torch.bfloat16 if bf16 else torch.float32
+    dzv = torch.empty((4, NR, geo.wc), device=dev, dtype=dt)
+    dbot = torch.empty((NR, geo.nw), device=dev, dtype=dt)
+    dz = torch.empty((8, NR, geo.nw), device=dev, dtype=dt)
+    dxp = torch.empty((R, 3), device=dev)
+    dzd = torch.empty((4, NR, geo.wd), device=dev, dtype=dt)
+    work = level.buffer("train_art", "work", 4, dev)
+    packed = _pack_bwd(P, dev, S, bf16)
+    enc_chain = enc if enc.shape[1] != geo.ne else _enc_tiled(enc, 16 if bf16 else 64)
+    ev = level.events(timers)
+    L.call("aon_mlp_art_bwd_bf16" if bf16 else "aon_mlp_art_bwd", L.ptr(packed), L.ptr(draw),
+           L.ptr(masks), L.ptr(enc_chain), R, L.ptr(dzv), L.ptr(dbot), L.ptr(dz), L.ptr(dxp),
+           L.ptr(dzd), L.ptr(work), L.stream(dev))
+    L.snapshot_pack(packed)  # the chain was the pack's last reader
+    level.record(timers, ev, f"art_bwd_chain{S}", R)
+    return dzv, dbot, dz, dxp, dzd, work
+
+
+def _backward_level_latent(geo, P, dlat, enc, S, draw, masks, bf16, timers=None):
+    """The latent-code gradients alone (``latent_only``: the MLPs are frozen): the chain as
+    _backward_level_fused launches it, then ONE aon_art_latent_grad on four of its tensors --
+    dl = (sum_rows dZ)^T W[:, latent columns] needs the column sums of dzv[0], dz[5], dz[0] and
+    dzd[0] (768 of the chain's 3,328 columns) and no activation; no weight gradient is formed
+    and no aon_gemm runs.  dlat = (dshape, dapp, dart), (1, n) each, overwritten."""
+    R, dev = draw.shape[0], draw.device
+    dzv, _, dz, _, dzd, _ = _chain(geo, P, enc, S, draw, masks, bf16, timers)
+    nbytes = L.lib().aon_art_latent_grad_workspace_bytes(R)
+    work = level.buffer("train_art", f"latent{nbytes}", nbytes, dev)  # sized by R: one per size
+    ev = level.events(timers)
+    L.call("aon_art_latent_grad", L.ctypes.byref(_params_struct(P)), L.ptr(dzv[0]), L.ptr(dz[5]),
+           L.ptr(dz[0]), L.ptr(dzd[0]), int(bf16), R, *(L.ptr(d) for d in dlat), L.ptr(work),
+           L.stream(dev))
+    level.record(timers, ev, f"art_dlatent{S}", R)
+
+
 def _backward_level_fused(geo, P, G, lat, dlat, xyz, enc, venc, S, hd, h, bot, hv, draw,
                           masks=None, h_tiled=True, enc_bf=None, timers=None, cfg=DEFAULT):
     """_backward_level with every input-gradient product (and pos_enc's backward) in one fused
@@ -275,23 +319,8 @@ def _backward_level_fused(geo, P, G, lat, dlat, xyz, enc, venc, S, hd, h, bot, h
     wd, nw, wc, ne, nv = geo.wd, geo.nw, geo.wc, geo.ne, geo.nv
     shape, app, art = lat
     dshape, dapp, dart = dlat
-    NR = tiles.rows(R)
-    dt = torch.bfloat16 if bf16 else torch.float32
-    dzv = torch.empty((4, NR, wc), device=dev, dtype=dt)
-    dbot = torch.empty((NR, nw), device=dev, dtype=dt)
-    dz = torch.empty((8, NR, nw), device=dev, dtype=dt)
-    dxp = torch.empty((R, 3), device=dev)
-    dzd = torch.empty((4, NR, wd), device=dev, dtype=dt)
-    work = level.buffer("train_art", "work", 4, dev)
-    packed = _pack_bwd(P, dev, S, bf16)
     enc_t = enc.shape[1] != ne  # the fused forward's tiled copy
-    enc_chain = enc if enc_t else _enc_tiled(enc, 16 if bf16 else 64)
-    ev = level.events(timers)
-    L.call("aon_mlp_art_bwd_bf16" if bf16 else "aon_mlp_art_bwd", L.ptr(packed), L.ptr(draw),
-           L.ptr(masks), L.ptr(enc_chain), R, L.ptr(dzv), L.ptr(dbot), L.ptr(dz), L.ptr(dxp),
-           L.ptr(dzd), L.ptr(work), L.stream(dev))
-    L.snapshot_pack(packed)  # the chain was the pack's last reader
-    level.record(timers, ev, f"art_bwd_chain{S}", R)
+    dzv, dbot, dz, dxp, dzd, work = _chain(geo, P, enc, S, draw, masks, bf16, timers)
     ev = level.events(timers)
 
     # the operands (level.Operand): d raw and dL/dx' row-major, the chain's gradients tiled (the
@@ -356,11 +385,13 @@ def _backward_level_fused(geo, P, G, lat, dlat, xyz, enc, venc, S, hd, h, bot, h
 class ArtRenderLevel(torch.autograd.Function):
     """cast_rays + articulated NeRFMLP + activations + volumetric_rendering of one level
     (model_autodecoder.py:296-333) with gradients for the level's 40 MLP parameters and the
-    three latent codes (density = shape, color = appearance, articulation)."""
+    three latent codes (density = shape, color = appearance, articulation).  ``latent_only``
+    (render_level): gradients for the codes alone -- the same forward and chain, then
+    _backward_level_latent instead of the weight gradients; no activation is kept."""
 
     @staticmethod
-    def forward(ctx, geo, cfg, timers, rays_o, rays_d, viewdirs, t_vals, white_bkgd, noise,
-                shape, app, art, *params):
+    def forward(ctx, geo, cfg, timers, latent_only, rays_o, rays_d, viewdirs, t_vals, white_bkgd,
+                noise, shape, app, art, *params):
         # cfg: the model's TrainNumerics; timers: a dict of hip events (bench.py) or None
         B, S = t_vals.shape
         R, dev = B * S, t_vals.device
@@ -394,10 +425,19 @@ class ArtRenderLevel(torch.autograd.Function):
                                                  exact_folds=cfg.bf16)
         comp, acc, depth, weights = level.composite_fwd(raw, t_vals, rays_d, white_bkgd,
                                                         L.ACT_ARTIC)
-        ctx.save_for_backward(rays_d, t_vals, xyz, enc, venc, raw, hd, h, bot, hv, *lat, *params)
-        ctx.masks = masks
         ctx.enc_bf = enc_bf if masks is not None else None
         ctx.h_tiled = masks is not None  # the fused forward keeps its tensors tiled
+        ctx.latent_only = latent_only
+        if latent_only:  # only what the chain and aon_art_latent_grad read
+            if masks is None:  # (the layer-by-layer forward: row-major activations)
+                masks = relu_masks(list(hd) + list(h) + list(hv), R)
+            ctx.bf16 = hd.dtype == torch.bfloat16  # as the kept activations, like the full backward
+            ctx.enc_bf = None
+            ctx.save_for_backward(rays_d, t_vals, enc, raw, *params)
+        else:
+            ctx.save_for_backward(rays_d, t_vals, xyz, enc, venc, raw, hd, h, bot, hv, *lat,
+                                  *params)
+        ctx.masks = masks
         ctx.meta = (geo, B, S, bool(white_bkgd), tuple(x.shape for x in (shape, app, art)))
         ctx.cfg, ctx.timers = cfg, timers
         ctx.mark_non_differentiable(weights)
@@ -409,6 +449,17 @@ class ArtRenderLevel(torch.autograd.Function):
     def backward(ctx, g_rgb, g_acc, g_depth, _g_w):
         geo, B, S, white, lat_shapes = ctx.meta
         saved = ctx.saved_tensors
+        if ctx.latent_only:
+            rays_d, t_vals, enc, raw = saved[:4]
+            params = saved[4:]
+            draw = level.composite_bwd(raw, t_vals, rays_d, B, S, white, L.ACT_ARTIC, g_rgb,
+                                       g_acc, g_depth)
+            P = [(params[2 * i], params[2 * i + 1]) for i in range(20)]
+            dlat = tuple(torch.empty((1, n), device=raw.device)
+                         for n in (geo.n_shape, geo.n_app, geo.n_art))
+            _backward_level_latent(geo, P, dlat, enc, S, draw, ctx.masks, ctx.bf16, ctx.timers)
+            dlat = [d.reshape(s) for d, s in zip(dlat, lat_shapes)]
+            return (None,) * 10 + (*dlat,) + (None,) * 40
         rays_d, t_vals, xyz, enc, venc, raw, hd, h, bot, hv = saved[:10]
         lat = saved[10:13]
         params = saved[13:]
@@ -429,20 +480,31 @@ class ArtRenderLevel(torch.autograd.Function):
             _backward_level(geo, P, G, lat, dlat, xyz, enc, venc, S, hd, h, bot, hv, draw)
         grads = [g for pair in G for g in pair]
         dlat = [d.reshape(s) for d, s in zip(dlat, lat_shapes)]
-        return (None, None, None, None, None, None, None, None, None, *dlat, *grads)
+        return (None, None, None, None, None, None, None, None, None, None, *dlat, *grads)
 
 
 def render_level(mlp, rays_o, rays_d, viewdirs, t_vals, white_bkgd, latents, noise=None,
-                 cfg=DEFAULT, timers=None):
+                 cfg=DEFAULT, timers=None, latent_only=False):
     """One NeRF_AE_Art level under autograd -> (comp_rgb, acc, depth, weights); ``cfg``: the
-    model's TrainNumerics."""
+    model's TrainNumerics.  ``latent_only``: the backward computes the latent codes' gradients
+    alone (aon_art_latent_grad after the fused chain: no weight gradient, no kept activation)
+    and returns None for every MLP parameter -- for fitting codes with the MLPs frozen
+    (latent_fit.py).  It needs every MLP parameter frozen and the fused backward (ValueError
+    otherwise, before any launch)."""
     params = [p for m in art_layers(mlp) for p in (m.weight, m.bias)]
     geo = level.geo_of(mlp)
     if not geo.default_depths:
         raise ValueError("the articulated training path implements the reference's default layer "
                          "counts (netdepth 8, skip 4, 4 deformation / 4 condition layers)")
-    return ArtRenderLevel.apply(geo, cfg, timers, rays_o, rays_d, viewdirs, t_vals,
-                                bool(white_bkgd), noise,
+    if latent_only:
+        if any(p.requires_grad for p in params):
+            raise ValueError("latent_only: an MLP parameter requires grad -- freeze the MLPs "
+                             "(latent_fit.freeze) or take the full backward (latent_only=False)")
+        if not (cfg.fused_backward and geo.fused_ok):
+            raise ValueError("latent_only needs the fused backward chain (TrainNumerics."
+                             "fused_backward and the default MLP geometry)")
+    return ArtRenderLevel.apply(geo, cfg, timers, bool(latent_only), rays_o, rays_d, viewdirs,
+                                t_vals, bool(white_bkgd), noise,
                                 latents["density"], latents["color"], latents["articulation"],
                                 *params)
 
@@ -512,15 +574,26 @@ def training_step(model, code_library, batch, randomized, white_bkgd, near, far,
     two levels' acc against batch["instance_mask"] (or batch["mask"]); ``mask_rgb`` takes the
     colour losses over the foreground rays only.  The whole loss is then one aon_loss_masked
     launch and ``logs`` gains ``opacity``.  With the defaults nothing changes."""
+    return step_on_latents(model, lambda: code_library(batch), batch, randomized, white_bkgd, near,
+                           far, u_coarse=u_coarse, u_fine=u_fine, timers=timers, opacity=opacity,
+                           opacity_lambda=opacity_lambda, mask_rgb=mask_rgb)
+
+
+def step_on_latents(model, lookup, batch, randomized, white_bkgd, near, far, *, u_coarse=None,
+                    u_fine=None, timers=None, opacity=None, opacity_lambda=0.05, mask_rgb=False,
+                    latent_only=False):
+    """training_step's forward and loss assembly on the latent dict ``lookup()`` returns (looked
+    up after the mask check, as training_step always did): shared with latent_fit.fit_step, which
+    passes ``latent_only`` on to the model."""
     masked = opacity is not None or mask_rgb
     if masked:
         mask = batch.get("instance_mask", batch.get("mask"))
         if mask is None:
             raise ValueError("training_step: opacity / mask_rgb need batch['instance_mask'] "
                              "(or batch['mask'])")
-    latents = code_library(batch)
+    latents = lookup()
     ret = model(batch, randomized, white_bkgd, near, far, latents, u_coarse=u_coarse,
-                u_fine=u_fine, timers=timers)
+                u_fine=u_fine, timers=timers, **({"latent_only": True} if latent_only else {}))
     reg = LatentReg.apply(latents["density"], latents["color"], latents["articulation"])
     if masked:
         loss, loss0, loss1, op, psnr0, psnr1 = masked_loss(

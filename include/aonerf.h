@@ -33,7 +33,7 @@ typedef void* aon_stream_t; /* hipStream_t */
                             * AON_PREC_F16X3 stream now has bottleneck_layer folded in);
                             * aon_ray_limits_box, aon_ray_limits, aon_sample_along_rays_bounds,
                             * aon_compact_rays, aon_scatter_payload and their workspace
-                            * queries */
+                            * queries; aon_art_latent_grad and its workspace query */
 
 /* Precision of the MLP GEMMs (see DESIGN.md "MLP precision modes"). */
 #define AON_PREC_FP32 0  /* exact fp32 MFMA (v_mfma_f32_16x16x4_f32) */
@@ -739,6 +739,32 @@ int aon_pos_enc_bwd(const float* x, int64_t ldx, const float* g_enc, int64_t ldg
  * an (n x c) code; grad (n x c) = weight / c * code / ||code[:, c]|| (0 on a zero column). */
 int aon_latent_reg(const float* code, int64_t n, int64_t c, float weight, int accumulate,
                    float* loss, float* grad, aon_stream_t stream);
+
+/* The latent-code gradients of one articulated level ALONE -- fitting the codes with the MLPs
+ * frozen (the reference's --is_optimize, utils.get_optimizer_latent_opt).  A layer z = W [x; l]
+ * + b with the code l on every row gives dL/dl = (sum_rows dZ)^T W[:, latent columns], so from
+ * four of aon_mlp_art_bwd[_bf16]'s outputs for the same N rows (tiled, NR = N rounded up to 16
+ * rows, UNSCALED as the chain stores them; rows N .. NR-1 are never read: the chain does not
+ * write them) -- dzv0 = dzv[0] (NR, 128), dz5 = dz[5] (NR, 256), dz0 = dz[0] (NR, 256), dzd0 =
+ * dzd[0] (NR, 128); bf16 = 0: fp32, 1: raw bf16 -- and the weights in `params` ([out][in], row
+ * stride w_cols; biases are not read):
+ *   dapp   (128) = colsum(dzv0)^T views_linear.0[:, 283:411],
+ *   dshape (128) = colsum(dz5)^T pts_linears.5[:, 319:447] + colsum(dz0)^T pts_linears.0[:, 63:191]
+ *                  + colsum(dzd0)^T deformations_linear.0[:, 3:131], added in that order,
+ *   dart   (32)  = colsum(dzd0)^T deformations_linear.0[:, 131:163],
+ * all fp32, overwritten.  Column sums: a number of workgroups fixed by N each sum a contiguous
+ * range of 16-row blocks in fp32 (bf16 inputs too) into `work`, summed again in a fixed order;
+ * the products are fmaf chains in a fixed order.  No floating-point atomics: two calls on the
+ * same input agree bit for bit.  Three stream-ordered launches, no allocation, no host
+ * synchronisation.  work: aon_art_latent_grad_workspace_bytes(N) bytes (0 from the query: N out
+ * of range), 16-byte aligned.  Refused (< 0) before any launch: a null pointer, N <= 0, bf16
+ * outside {0, 1}, a gradient tensor or work not 16-byte aligned, and a `params` table that is not
+ * the default geometry WITH its latent columns (w_cols >= 163, 191, 447, 411 for
+ * deformations_linear.0, pts_linears.0, pts_linears.5, views_linear.0), the layer named. */
+size_t aon_art_latent_grad_workspace_bytes(int64_t N);
+int aon_art_latent_grad(const aon_mlp_art_params* params, const void* dzv0, const void* dz5,
+                        const void* dz0, const void* dzd0, int bf16, int64_t N, float* dshape,
+                        float* dapp, float* dart, void* work, aon_stream_t stream);
 
 #ifdef __cplusplus
 }

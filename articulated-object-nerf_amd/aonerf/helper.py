@@ -223,6 +223,32 @@ def volumetric_rendering(rgb, density, t_vals, dirs, white_bkgd, nocs=None):
     return comp, acc, w, depth
 
 
+def composite_features(weights, feat):
+    """A per-sample feature composited with a render's weights (reference helper.py:191-193,
+    comp_nocs): weights (B, S), feat (B, S, C) or (B*S, C), 1 <= C <= 8 -> (B, C) =
+    sum_s weights[b, s] feat[b, s, :], on aon_composite_feat (summed in the order
+    aon_composite_fwd sums comp_rgb).  A 2-D ``feat`` may be a column slice of wider rows (unit
+    column stride): it is read in place."""
+    L.require_gpu(weights, feat)
+    if weights.dim() != 2:
+        raise ValueError("composite_features: weights must be (B, S)")
+    B, S = weights.shape
+    C = feat.shape[-1]
+    if feat.dim() not in (2, 3) or feat.numel() != B * S * C or not 1 <= C <= 8:
+        raise ValueError(f"composite_features: feat must be ({B}, {S}, C) or ({B * S}, C), "
+                         f"1 <= C <= 8, got {tuple(feat.shape)}")
+    if not 1 <= S <= 512:
+        raise ValueError("composite_features: 1 <= S <= 512")
+    weights = L.contig(weights.detach())
+    feat = feat.detach()
+    if not (feat.dim() == 2 and feat.stride(1) == 1 and feat.stride(0) >= C):
+        feat = L.contig(feat).reshape(B * S, C)
+    out = torch.empty((B, C), device=weights.device)
+    L.call("aon_composite_feat", L.ptr(weights), L.ptr(feat), feat.stride(0) if B * S > 1 else C,
+           C, B, S, L.ptr(out), L.stream(weights.device))
+    return out
+
+
 # ----------------------------------------------------------------------------- pdf sampling
 def _pdf_call(bins, weights, num_samples, randomized, u, t_merge, origins, directions,
               float_min_eps=2 ** -32):

@@ -175,6 +175,17 @@ def to8b(x):
     return out
 
 
+def canonical_to_rgb(canonical, acc, box_side_length=2, white_bkgd=True, eps=1e-6):
+    """A canonical-coordinate map (render maps=True: ``canonical`` (..., 3) = sum w x', ``acc``
+    (...) = sum w) as an image for to8b / store_image: the opacity-normalised coordinate
+    canonical / max(acc, eps) mapped from the box [-side/2, side/2]^3 to [0, 1]^3 (/ side + 0.5,
+    clipped), blended onto the white or black background by acc.  Once per frame: torch ops."""
+    a = acc.unsqueeze(-1)
+    nocs = ((canonical / a.clamp_min(eps)) / box_side_length + 0.5).clamp(0.0, 1.0)
+    a = a.clamp(0.0, 1.0)
+    return nocs * a + (1.0 - a) if white_bkgd else nocs * a
+
+
 def store_image(dirpath, rgbs, name):
     """models/utils.py:21-27: <name><iii>.jpg per image (PIL, as the reference)."""
     from PIL import Image

@@ -267,25 +267,33 @@ class LayerBuffers:
         return t[i] if self.kept else t[i & 1]
 
 
+def art_deformation(geo, P, bias, xyz, bufs):
+    """The deformation MLP of art_forward alone (model_autodecoder.py:196-205) -> delta (R, 3):
+    also what NeRFMLP.deform computes when the fused deformation pass is off or out of range."""
+    R, dev = xyz.shape[0], xyz.device
+    # deformation MLP on cat[xyz, shape, art] (:196-203), the latent columns folded
+    x = bufs.out("hd", 0)
+    linear_fwd(x, xyz, 3, P[geo.DEF0][0], bias(geo.DEF0), relu=True)
+    for i in range(1, geo.nd):
+        y = bufs.out("hd", i)
+        linear_fwd(y, x, geo.wd, *P[geo.DEF0 + i], relu=True)
+        x = y
+    delta = torch.empty((R, 3), device=dev)
+    linear_fwd(delta, x, geo.wd, *P[geo.DL])  # deformation_layer (:205)
+    x = y = None
+    if not bufs.kept:
+        del bufs.t["hd"]
+    return delta
+
+
 def art_forward(geo, P, bias, xyz, venc, S, bufs, noise=None):
     """The articulated NeRFMLP.forward (model_autodecoder.py:168-239) layer by layer on aon_gemm,
     on sample positions xyz (R, 3) and view encodings venc (R / S, nv): P the (weight, bias)
     pairs in art_layers order, ``bias(i)`` the folded bias of a layer that reads a latent code,
     ``bufs`` (LayerBuffers) the outputs' buffers -> (enc = pos_enc(x'), raw)."""
     R, dev = xyz.shape[0], xyz.device
-    wd, nw, wc, ne, nv = geo.wd, geo.nw, geo.wc, geo.ne, geo.nv
-    # deformation MLP on cat[xyz, shape, art] (:196-203), the latent columns folded
-    x = bufs.out("hd", 0)
-    linear_fwd(x, xyz, 3, P[geo.DEF0][0], bias(geo.DEF0), relu=True)
-    for i in range(1, geo.nd):
-        y = bufs.out("hd", i)
-        linear_fwd(y, x, wd, *P[geo.DEF0 + i], relu=True)
-        x = y
-    delta = torch.empty((R, 3), device=dev)
-    linear_fwd(delta, x, wd, *P[geo.DL])  # deformation_layer (:205)
-    x = y = None
-    if not bufs.kept:
-        del bufs.t["hd"]
+    nw, wc, ne, nv = geo.nw, geo.wc, geo.ne, geo.nv
+    delta = art_deformation(geo, P, bias, xyz, bufs)
     # x' = delta + xyz -> pos_enc (enc_after, :205-212); enc[:, :3] is x' itself
     enc = torch.empty((R, ne), device=dev)
     L.call("aon_cast_rays", L.ptr(xyz), None, None, R, 1, L.ptr(delta), 3, None, geo.min_deg,

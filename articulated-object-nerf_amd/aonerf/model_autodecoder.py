@@ -22,6 +22,7 @@ latent, one tiny GEMM each).  ``NeRFMLP.fused = False`` selects the layer-by-lay
 (level.art_forward, the walker the training path shares), every product on the f16x3 MFMA GEMM
 (aon_gemm): also the fallback when an activation leaves the fused kernel's fp16x3 range.
 """
+import warnings
 from types import SimpleNamespace
 
 import torch
@@ -29,9 +30,14 @@ import torch.nn as nn
 import torch.nn.init as init
 
 from . import _lib as L
+from . import helper
 from . import level as _level
 from . import two_level
 from .numerics import resolve as _resolve_numerics
+
+# what a render (two_level.render) and a deformation pass say when they leave the fused path
+RANGE_WARNING = ("NeRF_AE_Art: an MLP activation exceeded the fused fp16x3 range; "
+                 "re-rendered on the layer-by-layer path")
 
 
 class NeRFMLP(nn.Module):
@@ -171,6 +177,71 @@ class NeRFMLP(nn.Module):
         bufs = _level.LayerBuffers(geo, xyz.shape[0], xyz.device)
         return _level.art_forward(geo, P, fb.__getitem__, xyz, venc, S, bufs)[1]
 
+    # -- the deformation MLP alone (:196-205): x' = x + delta(x, shape, articulation)
+    @torch.no_grad()
+    def _deform_rows(self, latents, *, rays=None, pos=None, packed=None, range_check=True):
+        """(xp4 (N, 4) = [x', 0], d4 (N, 4) = [delta, ||delta||]) of the samples o + t d of
+        ``rays`` = (rays_o, rays_d, t_vals (B, S)) or of the points ``pos`` (N, 3): the fused
+        deformation pass (aon_mlp_art_fwd_deform[_points]) on ``packed`` (this MLP's stream
+        already packed with these latents; None: pack it), or layer by layer on aon_gemm
+        (_level.art_deformation) when ``fused`` is off -- or, with ``range_check`` (one sync, not
+        under stream capture), when the pass raised the pack's range flag."""
+        if rays is not None:
+            o, d, t = (L.contig(x) for x in rays)
+            L.require_gpu(o, d, t)
+            B, S = t.shape
+            N, dev = B * S, t.device
+        else:
+            L.require_gpu(pos)
+            pos = L.contig(pos)
+            N, dev = pos.shape[0], pos.device
+        if self._fused_ok():
+            buf = self.packed_weights(latents) if packed is None else packed
+            xp4, d4 = torch.empty((N, 4), device=dev), torch.empty((N, 4), device=dev)
+            if rays is not None:
+                L.call("aon_mlp_art_fwd_deform", L.ptr(buf), L.ptr(o), L.ptr(d), L.ptr(t), B, S,
+                       L.ptr(xp4), L.ptr(d4), L.stream(dev))
+            else:
+                L.call("aon_mlp_art_fwd_deform_points", L.ptr(buf), L.ptr(pos), N, L.ptr(xp4),
+                       L.ptr(d4), L.stream(dev))
+            if not (range_check and not torch.cuda.is_current_stream_capturing()
+                    and L.range_overflow([buf])):
+                return xp4, d4
+            warnings.warn(RANGE_WARNING, RuntimeWarning)
+        if rays is not None:
+            xyz = torch.empty((N, 3), device=dev)
+            L.call("aon_cast_rays", L.ptr(o), L.ptr(d), L.ptr(t), B, S, None, 0, L.ptr(xyz), 0, 0,
+                   None, L.stream(dev))
+        else:
+            xyz = pos
+        geo = _level.geo_of(self)
+        P = self._pairs()
+        fb = self._folded(P, latents)
+        delta = _level.art_deformation(geo, P, fb.__getitem__, xyz,
+                                       _level.LayerBuffers(geo, N, dev))
+        xp4, d4 = torch.zeros((N, 4), device=dev), torch.empty((N, 4), device=dev)
+        torch.add(delta, xyz, out=xp4[:, :3])
+        d4[:, :3] = delta
+        d4[:, 3] = (delta * delta).sum(-1).sqrt()
+        return xp4, d4
+
+    def deform_rays(self, rays_o, rays_d, t_vals, latents):
+        """The deformation field on the samples o + t d of one level: (xp (B, S, 3) the canonical
+        coordinate x' = x + delta the trunk encodes, delta (B, S, 3), mag (B, S) = ||delta||),
+        through the fused deformation pass (aon_mlp_art_fwd_deform); x' is the x' of
+        forward_rays' fused kernel bit for bit.  No backward."""
+        B, S = t_vals.shape
+        xp4, d4 = self._deform_rows(latents, rays=(rays_o, rays_d, t_vals))
+        return xp4[:, :3].view(B, S, 3), d4[:, :3].view(B, S, 3), d4[:, 3].view(B, S)
+
+    def deform(self, pos, latents):
+        """The same on given sample points pos (..., 3) -> (xp (..., 3), delta (..., 3), mag (...))."""
+        if pos.shape[-1] != 3:
+            raise ValueError("deform expects (..., 3) points")
+        lead = tuple(pos.shape[:-1])
+        xp4, d4 = self._deform_rows(latents, pos=pos.reshape(-1, 3))
+        return xp4[:, :3].view(lead + (3,)), d4[:, :3].view(lead + (3,)), d4[:, 3].view(lead)
+
     def forward(self, pos, condition, latents):
         """reference model_autodecoder.py:168-239: pos (B, S, 3) sample positions (enc_after),
         condition (B, 27) encoded view directions -> (raw_rgb (B, S, 3), raw_density (B, S, 1))."""
@@ -218,7 +289,7 @@ class NeRF_AE_Art(nn.Module):  # noqa: N801 (reference name)
 
     def forward(self, rays, randomized, white_bkgd, near, far, latents, train=True, *,
                 u_coarse=None, u_fine=None, return_weights=False, return_intermediates=False,
-                timers=None, latent_only=False):
+                timers=None, latent_only=False, maps=False):
         """reference model_autodecoder.py:278-337 -> [(comp_rgb, acc, depth)_coarse, (...)_fine]
         (``u_coarse`` / ``u_fine`` inject randomized-mode uniforms; the extras as NeRF.forward;
         ``timers`` (dict) records hip events around each level's MLP / composite launches).
@@ -228,17 +299,28 @@ class NeRF_AE_Art(nn.Module):  # noqa: N801 (reference name)
         aon_mlp_art_fwd_train, which also stores the activations, then the HIP backward into the
         MLP parameters and the latent codes); otherwise the fused inference kernel (two_level.py
         drives the two levels either way).  ``latent_only`` (the training path only): gradients
-        for the latent codes alone, the MLPs frozen (train_art.render_level; latent_fit.py)."""
+        for the latent codes alone, the MLPs frozen (train_art.render_level; latent_fit.py).
+
+        ``maps`` (inference only; ValueError on the training path, there is no backward): the
+        fine level's tuple ends with a dict of the deformation field composited with the fine
+        weights (helper.py:191-193's nocs hook) -- ``canonical`` (B, 3) = sum w x',
+        ``motion`` (B, 3) = sum w delta, ``motion_mag`` (B,) = sum w ||delta|| -- from one
+        deformation pass over the fine samples (aon_mlp_art_fwd_deform) and two
+        aon_composite_feat launches; every other output is unchanged."""
         o, d, v = rays["rays_o"], rays["rays_d"], rays["viewdirs"]
         L.require_gpu(o, d, v)
         o, d, v = L.contig(o), L.contig(d), L.contig(v)
         training = torch.is_grad_enabled() and (
             any(p.requires_grad for p in self.parameters())
             or any(x.requires_grad for x in latents.values()))
+        if maps and training:
+            raise ValueError("maps=True has no backward: call under torch.no_grad() or with "
+                             "frozen parameters and latent codes")
         run = two_level.train if training else two_level.render
+        kw = dict(maps=True) if maps else {}
         return run(self._spec(latents, latent_only), o, d, v, randomized, white_bkgd, near, far,
                    u_coarse=u_coarse, u_fine=u_fine, return_weights=return_weights,
-                   return_intermediates=return_intermediates, timers=timers)
+                   return_intermediates=return_intermediates, timers=timers, **kw)
 
     def _spec(self, latents, latent_only=False):
         mlps = (self.coarse_mlp, self.fine_mlp)
@@ -248,8 +330,22 @@ class NeRF_AE_Art(nn.Module):  # noqa: N801 (reference name)
             return render_level(mlp, o, d, v, t_vals, white_bkgd, latents, noise,
                                 self.train_numerics, timers, latent_only)
 
+        def level_maps(mlp, o, d, t_vals, weights, timers):
+            # the level's MLP has just packed mlp._art_packed with these latents: the pass reads
+            # its prefix in place (a re-pack would clear the status word the render checks)
+            ev = _level.events(timers)
+            xp4, d4 = mlp._deform_rows(
+                latents, rays=(o, d, t_vals), range_check=False,
+                packed=getattr(mlp, "_art_packed", None) if mlp._fused_ok() else None)
+            _level.record(timers, ev, "deform1", t_vals.numel())
+            ev = _level.events(timers)
+            motion = helper.composite_features(weights, d4)
+            canonical = helper.composite_features(weights, xp4[:, :3])
+            _level.record(timers, ev, "maps1", t_vals.numel())
+            return {"canonical": canonical, "motion": motion[:, :3], "motion_mag": motion[:, 3]}
+
         return SimpleNamespace(
-            model=self, train_level=train_level,
+            model=self, train_level=train_level, maps=level_maps,
             mlp_raw=lambda level, mlp, o, d, v, t_vals, act: mlp.forward_rays(
                 o, d, v, t_vals, latents, act=act),
             # model_autodecoder.py:321-323 always in the compositor (AON_ACT_ARTIC)
@@ -259,5 +355,4 @@ class NeRF_AE_Art(nn.Module):  # noqa: N801 (reference name)
             packs=lambda: [getattr(m, "_art_packed", None) for m in mlps],
             # (the layer-by-layer path's aon_gemm operands carry 2^-8: range 1.6e7, not 8188)
             fallback=lambda: two_level.switched(mlps, "fused", False),
-            warning="NeRF_AE_Art: an MLP activation exceeded the fused fp16x3 range; "
-                    "re-rendered on the layer-by-layer path")
+            warning=RANGE_WARNING)

@@ -22,23 +22,41 @@ def _chunks(B, chunk):
         yield i, min(i + chunk, B)
 
 
-def _render_box(model, rays, chunk, white_bkgd, box_side_length, cull, timers=None):
+MAP_KEYS = ("canonical", "motion", "motion_mag")  # columns 5:8, 8:11, 11 of a maps payload
+
+
+def _maps_kw(maps):
+    # only a model asked for maps sees the keyword (NeRF_AE_Art.forward; the vanilla model has
+    # no deformation and refuses it)
+    return {"maps": True} if maps else {}
+
+
+def _put_maps(out, i, j, m):
+    out[i:j, 5:8], out[i:j, 8:11], out[i:j, 11] = m["canonical"], m["motion"], m["motion_mag"]
+
+
+def _render_box(model, rays, chunk, white_bkgd, box_side_length, cull, timers=None, maps=False):
     """(B, 5) payload [rgb(3), depth, acc] of ``rays`` bounded by the box of side
     ``box_side_length`` around the origin.  The bounds are formed once over all the rays (the
     fill of get_ray_limits depends on the batch), not per chunk.  ``cull``: only the rays that
-    hit the box reach the MLPs (zero hits: no MLP launch); the others are background rows."""
+    hit the box reach the MLPs (zero hits: no MLP launch); the others are background rows.
+    ``maps``: (B, 12), the payload followed by canonical (3), motion (3), motion_mag -- zero on
+    a culled ray."""
     o, d, v = rays["rays_o"], rays["rays_d"], rays["viewdirs"]
     B, dev = o.shape[0], o.device
+    kw = _maps_kw(maps)
     if not cull:
         near, far = helper.get_ray_limits(o, d, box_side_length)
-        out = torch.empty((B, 5), device=dev)
+        out = torch.empty((B, 12 if maps else 5), device=dev)
         for i, j in _chunks(B, chunk):
             sub = {k: x[i:j] for k, x in rays.items()}
             fine = model(sub, False, white_bkgd, near[i:j], far[i:j], timers=timers,
-                         fine_only=True)[1]
+                         fine_only=True, **kw)[1]
             out[i:j, 0:3] = fine[0]
             out[i:j, 3] = fine[2]
             out[i:j, 4] = fine[1]
+            if maps:
+                _put_maps(out, i, j, fine[-1])
         return out
     if torch.cuda.is_current_stream_capturing():
         raise ValueError("box culling reads the hit count on the host, which a stream capture "
@@ -48,18 +66,32 @@ def _render_box(model, rays, chunk, white_bkgd, box_side_length, cull, timers=No
     n = int(c["n_hit"].item())  # the one 4-byte read-back of the call
     comp = torch.empty((n, 3), device=dev)
     acc, depth = torch.empty((n,), device=dev), torch.empty((n,), device=dev)
+    hit = torch.empty((n, 12), device=dev) if maps else None  # columns 5.. : the hit rays' maps
     for i, j in _chunks(n, chunk):
         sub = {k: c[k][i:j] for k in ("rays_o", "rays_d", "viewdirs")}
         fine = model(sub, False, white_bkgd, c["near"][i:j], c["far"][i:j], timers=timers,
-                     fine_only=True)[1]
+                     fine_only=True, **kw)[1]
         comp[i:j], acc[i:j], depth[i:j] = fine[0], fine[1], fine[2]
-    return helper.scatter_payload(comp, acc, depth, c["slot"], white_bkgd)
+        if maps:
+            _put_maps(hit, i, j, fine[-1])
+    out = helper.scatter_payload(comp, acc, depth, c["slot"], white_bkgd)
+    if not maps:
+        return out
+    # the maps through the same scatter kernel, on a black background: a miss is a zero row
+    a = helper.scatter_payload(hit[:, 5:8], hit[:, 11], hit[:, 8], c["slot"], False)
+    b = helper.scatter_payload(hit[:, 8:11], hit[:, 11], hit[:, 8], c["slot"], False)
+    return torch.cat([out, a[:, 0:3], b[:, 0:3], a[:, 4:5]], 1)
 
 
 @torch.no_grad()
-def render_rays(model, batch, chunk, white_bkgd, near, far, box_side_length=None, cull=True):
+def render_rays(model, batch, chunk, white_bkgd, near, far, box_side_length=None, cull=True,
+                maps=False):
     """LitNeRF.render_rays (model.py:295-321): fine-level comp_rgb/acc/depth over all rays and
     psnr_legacy against batch['target'] (returned as 'psnr' instead of being logged).
+
+    ``maps`` (a model with a deformation field: NeRF_AE_Art.forward(maps=True)): also
+    'canonical' (B, 3), 'motion' (B, 3) and 'motion_mag' (B,), concatenated over the chunks like
+    comp_rgb; zero on a ray that box culling dropped.
 
     ``box_side_length`` (default None: ``near`` / ``far`` as given): bound every ray by the box
     of that side around the origin instead (helper.get_ray_limits; ``near`` / ``far`` are then
@@ -69,19 +101,24 @@ def render_rays(model, batch, chunk, white_bkgd, near, far, box_side_length=None
     B = batch["rays_o"].shape[0]
     if box_side_length is not None:
         rays = {k: batch[k] for k in ("rays_o", "rays_d", "viewdirs")}
-        p = _render_box(model, rays, chunk, white_bkgd, box_side_length, cull)
+        p = _render_box(model, rays, chunk, white_bkgd, box_side_length, cull, maps=maps)
         out = {"comp_rgb": p[:, 0:3].contiguous(), "acc": p[:, 4].contiguous(),
                "depth": p[:, 3].contiguous()}
+        if maps:
+            out.update(canonical=p[:, 5:8].contiguous(), motion=p[:, 8:11].contiguous(),
+                       motion_mag=p[:, 11].contiguous())
         if "target" in batch:
             out["psnr"] = interface.psnr_legacy(out["comp_rgb"], batch["target"]).mean()
         return out
     ret = defaultdict(list)
     for i, j in _chunks(B, chunk):
         sub = {k: batch[k][i:j] for k in ("rays_o", "rays_d", "viewdirs")}
-        fine = model(sub, False, white_bkgd, near, far, fine_only=True)[1]
+        fine = model(sub, False, white_bkgd, near, far, fine_only=True, **_maps_kw(maps))[1]
         ret["comp_rgb"].append(fine[0])
         ret["acc"].append(fine[1])
         ret["depth"].append(fine[2])
+        for k in MAP_KEYS if maps else ():
+            ret[k].append(fine[-1][k])
     out = {k: torch.cat(v, 0) for k, v in ret.items()}
     if "target" in batch:
         out["psnr"] = interface.psnr_legacy(out["comp_rgb"], batch["target"]).mean()
@@ -102,21 +139,26 @@ def render_rays_test(model, batch, chunk, white_bkgd, near, far):
 
 @torch.no_grad()
 def render_frame(model, c2w, H, W, focal, near=2.0, far=6.0, white_bkgd=True, p0=0, n=None,
-                 chunk=None, timers=None, box_side_length=None, cull=True):
+                 chunk=None, timers=None, box_side_length=None, cull=True, maps=False):
     """Fused ray generation + two-level render of pixels [p0, p0+n) of an H x W frame.
     Returns (n, 5) = [rgb(3), depth, acc] per pixel (the payload of the frame gather).
-    ``box_side_length`` / ``cull``: as render_rays (the bounds are formed over the n pixels)."""
+    ``box_side_length`` / ``cull``: as render_rays (the bounds are formed over the n pixels).
+    ``maps`` (as render_rays): (n, 12), the payload followed by canonical (3), motion (3) and
+    motion_mag."""
     n = H * W - p0 if n is None else n
     rays = frame_rays(c2w, H, W, focal, p0, n)
     if box_side_length is not None:
-        return _render_box(model, rays, chunk, white_bkgd, box_side_length, cull, timers)
-    out = torch.empty((n, 5), device=rays["rays_o"].device)
+        return _render_box(model, rays, chunk, white_bkgd, box_side_length, cull, timers, maps)
+    out = torch.empty((n, 12 if maps else 5), device=rays["rays_o"].device)
     for i, j in _chunks(n, chunk):
         sub = {k: v[i:j] for k, v in rays.items()}
-        fine = model(sub, False, white_bkgd, near, far, timers=timers, fine_only=True)[1]
+        fine = model(sub, False, white_bkgd, near, far, timers=timers, fine_only=True,
+                     **_maps_kw(maps))[1]
         out[i:j, 0:3] = fine[0]
         out[i:j, 3] = fine[2]
         out[i:j, 4] = fine[1]
+        if maps:
+            _put_maps(out, i, j, fine[-1])
     return out
 
 

@@ -12,6 +12,8 @@ Each model describes itself per forward with a ``spec``, a plain object of what 
     train_level(level, mlp, o, d, v, t_vals, white_bkgd, noise, timers) -> comp, acc, depth, w
     range_checked(), packs(), fallback(), warning   the range guard: whether to look, the packs
         with the status words, a context manager onto the model's exact path, the warning's text
+    maps(mlp, o, d, t_vals, weights, timers) -> dict   (render(maps=True) only) per-ray maps of
+        the fine level from its samples and weights, appended to the fine level's tuple
 
 Both models launch what they launched before they shared this: same entry points, arguments,
 order, allocations and random draws."""
@@ -121,7 +123,7 @@ def train(spec, o, d, v, randomized, white_bkgd, near, far, *, u_coarse=None, u_
 
 
 def _render_pass(spec, o, d, v, randomized, white_bkgd, near, far, u_coarse, u_fine,
-                 return_weights, return_intermediates, timers, fine_only):
+                 return_weights, return_intermediates, timers, fine_only, maps=False):
     m = spec.model
     B, dev = o.shape[0], o.device
     want_w = return_weights or return_intermediates
@@ -155,20 +157,24 @@ def _render_pass(spec, o, d, v, randomized, white_bkgd, near, far, u_coarse, u_f
         extras = {"t_vals": t_vals, "weights": weights, spec.extras_key: raw}
         ret.append(None if fine_only and level == 0 else shape_output(
             comp, acc, depth, weights, extras, return_weights, return_intermediates))
+        if maps and level == 1:
+            ret[1] = ret[1] + (spec.maps(mlp, o, d, t_vals, weights, timers),)
     return ret
 
 
 @torch.no_grad()
 def render(spec, o, d, v, randomized, white_bkgd, near, far, *, u_coarse=None, u_fine=None,
-           return_weights=False, return_intermediates=False, timers=None, fine_only=False):
-    """Both levels on the inference kernels.  ``fine_only`` (ignored when weights or
+           return_weights=False, return_intermediates=False, timers=None, fine_only=False,
+           maps=False):
+    """Both levels on the inference kernels.  ``maps``: the fine level's tuple ends with
+    spec.maps' dict (inside the range fallback too, so on the exact path when it is taken).  ``fine_only`` (ignored when weights or
     intermediates are asked for): the coarse entry is None.  If the range guard reports an
     activation outside the fp16x3 range (one sync per forward, skipped under HIP-graph capture)
     the outputs are invalid: render again inside spec.fallback(), with the same random draws,
     which leaves the generator where one forward leaves it."""
     fine_only = bool(fine_only) and not (return_weights or return_intermediates)
     args = (spec, o, d, v, randomized, white_bkgd, near, far, u_coarse, u_fine, return_weights,
-            return_intermediates, timers, fine_only)
+            return_intermediates, timers, fine_only, bool(maps))
     rng = torch.cuda.get_rng_state(o.device) if randomized else None
     ret = _render_pass(*args)
     if (spec.range_checked() and not torch.cuda.is_current_stream_capturing()

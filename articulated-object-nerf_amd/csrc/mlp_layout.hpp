@@ -305,6 +305,55 @@ constexpr bool layout_sigma_ok() {
 }
 static_assert(layout_sigma_ok(), "the density-only pass must be a prefix of the folded stream");
 static_assert(NetArtH::ok(), "inconsistent articulated fp16x3 layout");
+
+// The deformation-only pass (aon_mlp_art_fwd_deform: x' and the deformation of a render's
+// samples, without the trunk and the view branch): deformations_linear.0-3 and deformation_layer,
+// the first A_DOUT + 1 layers of kLayersArt.  The head is consumed before pts_linears.0, so the
+// pass reads a PREFIX of the packed articulated stream in place: same buffer, same bias table
+// and status word (behind the whole stream's NetArtH::kStreamBytes, not behind the prefix).  Its
+// 216 blocks round up to whole ring chunks of 16 (mlp_art_deform.hip's ring; the last chunk then
+// copies 8 of pts_linears.0's blocks, never read); only the prefix's 528 bias rows are staged.
+constexpr int kNumLayersArtDeform = A_DOUT + 1;
+constexpr int kBlocksArtDeform = 216;
+constexpr int kChunkArtDeform = 16;  // 1-KB blocks per ring chunk of the deformation-only pass
+constexpr int kStreamBlocksArtDeform =
+    (kBlocksArtDeform + kChunkArtDeform - 1) / kChunkArtDeform * kChunkArtDeform;  // 224
+constexpr int kBiasFloatsArtDeform = 528;
+struct NetArtDeformH {  // NetH's interface over the prefix (NetH::ok() wants whole 64-block streams)
+  static constexpr const LayerDesc* kTable = kLayersArt;
+  static constexpr bool kZeroBias = false;
+  static constexpr int kNumLayers = kNumLayersArtDeform;
+  static constexpr int kBlocks = kBlocksArtDeform;
+  static constexpr int kStreamBlocks = kStreamBlocksArtDeform;
+  static constexpr int kBiasFloats = kBiasFloatsArtDeform;
+  static constexpr LayerDesc layer(int i) { return kLayersArt[i]; }
+};
+// the prefix matches the articulated stream block for block and bias offset for bias offset: the
+// table is the same array, and the prefix ends where pts_linears.0 begins
+constexpr bool layout_art_deform_ok() {
+  int blk = 0, bias = 0;
+  for (int i = 0; i < kNumLayersArtDeform; ++i) {
+    const LayerDesc s = NetArtDeformH::layer(i);
+    const LayerDesc a = NetArtH::layer(i);
+    if (s.ka != a.ka || s.kb != a.kb || s.u != a.u || s.len_a != a.len_a || s.len_b != a.len_b ||
+        s.out_real != a.out_real || s.blk0 != a.blk0 || s.bias0 != a.bias0)
+      return false;
+    if (a.blk0 != blk || a.bias0 != bias) return false;
+    blk += (a.ka + a.kb) * a.u * 2;
+    bias += a.u * 16;
+  }
+  return blk == kBlocksArtDeform && bias == kBiasFloatsArtDeform &&
+         kLayersArt[A_P0].blk0 == kBlocksArtDeform &&
+         kLayersArt[A_P0].bias0 == kBiasFloatsArtDeform && kBiasFloatsArtDeform % 4 == 0 &&
+         kStreamBlocksArtDeform >= kBlocksArtDeform &&
+         kStreamBlocksArtDeform <= NetArtH::kStreamBlocks &&
+         // whole ring chunks, the last one holding a block the pass reads: every copy the ring
+         // issues is waited for (DmaPipe::begin) before the kernel ends
+         kStreamBlocksArtDeform % kChunkArtDeform == 0 &&
+         (kBlocksArtDeform - 1) / kChunkArtDeform == kStreamBlocksArtDeform / kChunkArtDeform - 1;
+}
+static_assert(layout_art_deform_ok(),
+              "the deformation-only pass must be a prefix of the articulated stream");
 static_assert(NetBwdH::ok(), "inconsistent backward-chain fp16x3 layout");
 static_assert(NetArtBwdH::ok(), "inconsistent articulated backward-chain fp16x3 layout");
 

@@ -474,6 +474,23 @@ int aon_mlp_art_bwd_bf16(const void* packed, const float* draw, const uint32_t* 
 int aon_mlp_art_fwd_points(const void* packed, const float* pos, const float* condition,
                            int64_t B, int S, int act, float* out, aon_stream_t stream);
 
+/* x' and Δ of the articulated deformation MLP alone (model_autodecoder.py:196-205), from a
+ * prefix of aon_mlp_art_pack's stream (latents folded into its biases as for aon_mlp_art_fwd).
+ * xp    (B*S, 4) = [x'0, x'1, x'2, 0]        or NULL
+ * delta (B*S, 4) = [Δ0, Δ1, Δ2, ||Δ||]       or NULL   (not both NULL)
+ * ||Δ|| = sqrt_rn(add_rn(add_rn(mul_rn(Δ0,Δ0), mul_rn(Δ1,Δ1)), mul_rn(Δ2,Δ2))).
+ * x' is the x' aon_mlp_art_fwd forms on chip, bit for bit (the same arithmetic for o + t d, the
+ * four layers, the head and the fp32 add), and Δ + (o + t d) = x' in fp32.  packed, xp and
+ * delta 16-byte aligned; rows past B*S are never written.  A value outside the fp16x3 range sets
+ * the pack's status word (aon_mlp_read_status), as in aon_mlp_art_fwd.  No allocation, no
+ * synchronisation.  (Added since ABI 13, without a version change.) */
+int aon_mlp_art_fwd_deform(const void* packed, const float* rays_o, const float* rays_d,
+                           const float* t, int64_t B, int S, float* xp, float* delta,
+                           aon_stream_t stream);
+/* The same on given sample points pos (N, 3). */
+int aon_mlp_art_fwd_deform_points(const void* packed, const float* pos, int64_t N,
+                                  float* xp, float* delta, aon_stream_t stream);
+
 /* ---------------------------------------------------------------- compositing */
 /* volumetric_rendering (helper.py:157-195) with the activations of model.py:186-187.
  * rgb: (B*S) rows of rgb_stride floats (3 = API tensor, 4 = fused raw buffer);
@@ -482,6 +499,15 @@ int aon_composite_fwd(const float* rgb, int64_t rgb_stride, const float* sigma,
                       int64_t sigma_stride, const float* t, const float* dirs, int64_t B,
                       int S, int white_bkgd, int act, float* comp_rgb, float* acc,
                       float* weights, float* depth, aon_stream_t stream);
+
+/* A per-sample feature composited with a render's weights (helper.py:191-193, comp_nocs):
+ * out (B, C) = sum_s weights[b, s] * feat[(b*S + s)*feat_stride + c], 1 <= C <= 8,
+ * 1 <= S <= 512, feat_stride >= C; summed in the order aon_composite_fwd sums comp_rgb, so a
+ * 3-channel call on its weights equals its comp_rgb (white_bkgd = 0) bit for bit.  feat holds
+ * B*S rows of feat_stride floats, each read once (one 16-byte load per row when feat_stride == 4,
+ * C <= 4 and feat is 16-byte aligned).  (Added since ABI 13, without a version change.) */
+int aon_composite_feat(const float* weights, const float* feat, int64_t feat_stride, int C,
+                       int64_t B, int S, float* out, aon_stream_t stream);
 
 /* ---------------------------------------------------------------- evaluation */
 /* Per-image mean squared error of n_images images of `pixels` rgb pixels ((n, P, 3) fp32):

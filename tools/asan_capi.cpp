@@ -49,6 +49,23 @@ int main() {
   expect_invalid(aon_composite_fwd(dummy, 2, dummy, 1, dummy, dummy, 4, 8, 1, 0, dummy, dummy,
                                    nullptr, dummy, nullptr),
                  "composite_fwd rgb_stride < 3");
+  expect_invalid(aon_composite_feat(dummy, dummy, 4, 9, 4, 8, dummy, nullptr), "composite_feat C = 9");
+  expect_invalid(aon_composite_feat(dummy, dummy, 4, 3, 4, 513, dummy, nullptr),
+                 "composite_feat S = 513");
+  expect_invalid(aon_composite_feat(dummy, dummy, 2, 3, 4, 8, dummy, nullptr),
+                 "composite_feat feat_stride < C");
+  expect_invalid(aon_composite_feat(dummy, nullptr, 4, 3, 4, 8, dummy, nullptr),
+                 "composite_feat null feat");
+  expect_invalid(aon_mlp_art_fwd_deform(p, dummy, dummy, dummy, 4, 8, nullptr, nullptr, nullptr),
+                 "art_fwd_deform no output");
+  expect_invalid(aon_mlp_art_fwd_deform(p, dummy, dummy, dummy, 4, 0, dummy, dummy, nullptr),
+                 "art_fwd_deform S = 0");
+  expect_invalid(aon_mlp_art_fwd_deform(p, dummy, nullptr, dummy, 4, 8, dummy, dummy, nullptr),
+                 "art_fwd_deform null rays_d");
+  expect_invalid(aon_mlp_art_fwd_deform_points(p, nullptr, 4, dummy, dummy, nullptr),
+                 "art_fwd_deform_points null pos");
+  expect_invalid(aon_mlp_art_fwd_deform_points(p, dummy, -1, dummy, dummy, nullptr),
+                 "art_fwd_deform_points N < 0");
   expect_invalid(aon_mlp_pack(nullptr, AON_PREC_F16X3, p, nullptr), "mlp_pack null params");
   aon_mlp_params prm;
   std::memset(&prm, 0, sizeof(prm));

@@ -200,7 +200,7 @@ class Geo:
                                and mlp.netdepth_deformation == 4 and mlp.netdepth_condition == 4
                                and mlp.input_ch == 3 and mlp.input_ch_view == 3
                                and mlp.num_rgb_channels == 3 and mlp.num_density_channels == 1)
-        # the fused kernels are compiled for the default geometry (mlp_layout.hpp kLayersArt)
+        # the fused kernels are compiled for the default geometry (mlp_layout.hpp kShapeArt)
         self.fused_ok = (self.default_depths and mlp.netwidth == 256
                          and mlp.netwidth_deformation == 128 and mlp.netwidth_condition == 128
                          and mlp.min_deg_point == 0 and mlp.max_deg_point == 10

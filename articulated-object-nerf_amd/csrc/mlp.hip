@@ -32,7 +32,7 @@ __device__ __forceinline__ f4 mfma(float a, float b, f4 c) {
 template <int LAYER, int NA, int NB, int NACC>
 __device__ __forceinline__ void gemm(Pipe<kThreads>& p, const f4 (&xa)[NA], const f4 (&xb)[NB],
                                      f4 (&acc)[NACC]) {
-  constexpr LayerDesc d = kLayers[LAYER];
+  constexpr LayerDesc d = kLayout32.layer[LAYER];
   constexpr int U = d.u;
   static_assert(U % 4 == 0 && U <= NACC && d.ka <= NA && d.kb <= NB, "layer/array mismatch");
 #pragma unroll
@@ -57,7 +57,7 @@ __device__ __forceinline__ void gemm(Pipe<kThreads>& p, const f4 (&xa)[NA], cons
 // single output tile (density / rgb heads): two interleaved accumulators over t
 template <int LAYER, int NA>
 __device__ __forceinline__ f4 gemm_u1(Pipe<kThreads>& p, const f4 (&xa)[NA], f4 init) {
-  constexpr LayerDesc d = kLayers[LAYER];
+  constexpr LayerDesc d = kLayout32.layer[LAYER];
   static_assert(d.u == 1 && d.kb == 0 && d.ka <= NA && d.ka % 2 == 0, "head layer shape");
   f4 acc0 = init, acc1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -76,7 +76,7 @@ __device__ __forceinline__ f4 gemm_u1(Pipe<kThreads>& p, const f4 (&xa)[NA], f4 
 
 template <int LAYER, int N>
 __device__ __forceinline__ void init_bias(f4 (&acc)[N], const float* bias_s, int g) {
-  constexpr LayerDesc d = kLayers[LAYER];
+  constexpr LayerDesc d = kLayout32.layer[LAYER];
 #pragma unroll
   for (int u = 0; u < d.u; ++u) acc[u] = *reinterpret_cast<const f4*>(bias_s + d.bias0 + 16 * u + 4 * g);
 }
@@ -185,7 +185,7 @@ __global__ __launch_bounds__(kThreads, 2) void k_mlp_fwd_f32(
   relu_into(h, acc);
 
   // density head on the layer-7 features (model.py:105-107): row 0 of the tile
-  const f4 dens = gemm_u1<LDEN>(p, h, *reinterpret_cast<const f4*>(bias_s + kLayers[LDEN].bias0 + 4 * g));
+  const f4 dens = gemm_u1<LDEN>(p, h, *reinterpret_cast<const f4*>(bias_s + kLayout32.layer[LDEN].bias0 + 4 * g));
 
   // bottleneck, no activation (model.py:109)
   init_bias<LBOT>(acc, bias_s, g);
@@ -200,7 +200,7 @@ __global__ __launch_bounds__(kThreads, 2) void k_mlp_fwd_f32(
   relu_into(h, vacc);
 
   // rgb head (model.py:118): rows 0..2 of the tile
-  const f4 rgb = gemm_u1<LRGB>(p, h, *reinterpret_cast<const f4*>(bias_s + kLayers[LRGB].bias0 + 4 * g));
+  const f4 rgb = gemm_u1<LRGB>(p, h, *reinterpret_cast<const f4*>(bias_s + kLayout32.layer[LRGB].bias0 + 4 * g));
 
   if (g == 0 && row < N) {
     const f4 o = {act_rgb(rgb[0], act), act_rgb(rgb[1], act), act_rgb(rgb[2], act),
@@ -255,7 +255,7 @@ using namespace aon::mlp;
 extern "C" size_t aon_mlp_packed_bytes(int precision) {
   // fp32 and the training streams use the same block grid: fp32 tiles, or hi+lo fp16 pairs of
   // equal size (bf16: bf16 weights in the hi blocks); the fp16x3 render stream has no bottleneck
-  // layer (mlp_layout.hpp kLayersHFold)
+  // layer (mlp_layout.hpp kLayoutHFold)
   if (precision == AON_PREC_F16X3) return NetVanillaFoldH::kPackedBytes;
   if (precision == AON_PREC_FP32 || precision == AON_PREC_F16X3_TRAIN || precision == AON_PREC_BF16)
     return kPackedBytesF32;
@@ -297,13 +297,12 @@ extern "C" int aon_mlp_pack(const aon_mlp_params* prm, int precision, void* pack
   a.w[LBOT] = prm->bottleneck_w; a.b[LBOT] = prm->bottleneck_b;
   a.w[LVIEW] = prm->views_w;     a.b[LVIEW] = prm->views_b;
   a.w[LRGB] = prm->rgb_w;        a.b[LRGB] = prm->rgb_b;
-  for (int i = 0; i < kNumLayers; ++i) {
-    AON_REQUIRE(a.w[i] && a.b[i], "null layer parameter");
-    a.layers[i] = precision == AON_PREC_FP32 ? kLayers[i] : kLayersH[i];
-  }
+  for (int i = 0; i < kNumLayers; ++i) AON_REQUIRE(a.w[i] && a.b[i], "null layer parameter");
+  // the fp16x3 grid's streams take their layer tables from their net types (fill_net)
   if (precision != AON_PREC_FP32)
     return pack_f16x3(a, packed, (hipStream_t)stream, precision == AON_PREC_BF16,
                       precision == AON_PREC_F16X3);
+  for (int i = 0; i < kNumLayers; ++i) a.layers[i] = kLayout32.layer[i];
   // the fp32 kernels never set the range-status word: cleared once here
   const hipError_t e = hipMemsetAsync(static_cast<char*>(packed) + kPackedBytesF32 - kStatusBytes, 0,
                                       kStatusBytes, (hipStream_t)stream);

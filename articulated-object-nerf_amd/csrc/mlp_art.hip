@@ -10,7 +10,7 @@
 //   optional padded sigmoid / softplus(raw - 1) (model_autodecoder.py:321-323)
 //
 // The latent columns are folded into per-call biases by the host (NeRFMLP.folded_biases), so
-// the stream (mlp_layout.hpp kLayersArt) holds only per-sample columns.  The deformation head's
+// the stream (mlp_layout.hpp kShapeArt) holds only per-sample columns.  The deformation head's
 // output lands in lane group 0 (rows 0..2 of its tile, column = sample); it is broadcast to the
 // sample's other three lane groups with ds_bpermute, added to xyz in fp32 and encoded in
 // registers, so nothing leaves the chip between the deformation and the raw outputs.

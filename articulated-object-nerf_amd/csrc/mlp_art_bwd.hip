@@ -7,7 +7,7 @@
 // stored for the weight-gradient GEMMs (dW = dZ^T X, train_art.py).
 //
 // Structure and numerics as mlp_bwd.hip (the vanilla chain): feature-major MFMA tiles, W^T
-// streamed through the LDS-DMA ring (kLayersArtBwd, packed from the forward weights with tr = 1),
+// streamed through the LDS-DMA ring (kShapeArtBwd, packed from the forward weights with tr = 1),
 // each finished output pair converted in registers into the next layer's B fragments, gradients
 // at a per-call power-of-two scale s from max |d raw|.  The enc columns of the skip layer give
 // 64 values per sample, parked lane-private in LDS; those of pts_linears.0 join them in the
@@ -356,8 +356,6 @@ static int art_bwd_pack(const aon_mlp_art_params* prm, void* packed, aon_stream_
   AON_REQUIRE(aligned16(packed), "packed buffer must be 16-byte aligned");
   if (check_mlp_art_params(prm, bf16 ? "aon_mlp_art_bwd_pack_bf16" : "aon_mlp_art_bwd_pack"))
     return -1;
-  const int ld_view0 = (int)prm->w_cols[kArtView0], ld_pts5 = (int)prm->w_cols[kArtPts5];
-  const int ld_pts0 = (int)prm->w_cols[kArtPts0];
   PackArgsH a{};
   fill_net<NetArtBwdH>(a);
   const float* w[kNumLayersArtBwd] = {
@@ -366,18 +364,22 @@ static int art_bwd_pack(const aon_mlp_art_params* prm, void* packed, aon_stream_
       prm->pts_w[5] ? prm->pts_w[5] + 256 : nullptr,  // enc columns of the skip layer
       prm->pts_w[4], prm->pts_w[3], prm->pts_w[2], prm->pts_w[1], prm->pts_w[0],
       prm->deformation_w, prm->def_w[3], prm->def_w[2], prm->def_w[1]};
-  // row strides of the forward weights (their in-features, latent columns included)
-  const int ld[kNumLayersArtBwd] = {128, 128, 128, 128, ld_view0, 256, 256, 256, ld_pts5,
-                                    ld_pts5, 256, 256, 256, 256, ld_pts0, 128, 128, 128, 128};
+  // the forward layer behind each row; the row stride of its weight is its in-features (latent
+  // columns included: the caller's width)
+  static_assert(sizeof(kArtShape) / sizeof(kArtShape[0]) == kNumLayersArt && A_P0 == kArtPts0 &&
+                    A_P5 == kArtPts5 && A_V0 == kArtView0,
+                "A_D0..A_RGB index kArtShape");
+  const int fwd[kNumLayersArtBwd] = {A_RGB, A_V3, A_V2, A_V1, A_V0, A_BOT, A_P7, A_P6, A_P5, A_P5,
+                                     A_P4,  A_P3, A_P2, A_P1, A_P0, A_DOUT, A_D3, A_D2, A_D1};
   for (int i = 0; i < kNumLayersArtBwd; ++i) {
     AON_REQUIRE(w[i], "null layer weight");
     a.w[i] = w[i];
-    a.ldw[i] = ld[i];
+    a.ldw[i] = kArtShape[fwd[i]].latent ? (int)prm->w_cols[fwd[i]] : kArtShape[fwd[i]].in;
     a.tr[i] = 1;
   }
   AON_REQUIRE(prm->density_w, "null layer weight");
   a.w2[AB_BOTDEN] = prm->density_w;  // segment B of d h7: density_layer^T (1 x 256)
-  a.ldw2[AB_BOTDEN] = 256;
+  a.ldw2[AB_BOTDEN] = kArtShape[A_DEN].in;
   a.bf16 = bf16 ? 1 : 0;
   return pack_h(a, packed, (hipStream_t)stream);
 }

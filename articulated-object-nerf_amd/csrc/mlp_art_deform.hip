@@ -7,8 +7,8 @@
 //
 // -- the canonical coordinate x' and the deformation of every sample, which the full kernel
 // (k_mlp_art_f16x3) keeps on chip.  The pass reads the deformation PREFIX of an aon_mlp_art_pack
-// stream in place (mlp_layout.hpp NetArtDeformH: 216 of its 2,752 blocks, 528 of its bias rows,
-// its status word), with the full kernel's arithmetic for xyz, the four layers, the head and the
+// stream in place (mlp_layout.hpp NetArtDeformH: kBlocks of NetArtH's blocks, kBiasFloats of its
+// bias rows, its status word), with the full kernel's arithmetic for xyz, the four layers, the head and the
 // fp32 add, so x' is the full kernel's x' bit for bit.
 //
 // Budget.  No trunk, no pos_enc, no view branch: the widest layer is 128, so a wave's two
@@ -26,8 +26,8 @@
 namespace aon {
 namespace mlp {
 
-constexpr int kDeformLdsWeights = kRing * kChunkArtDeform * 64;                   // f4
-constexpr int kDeformLdsF4 = kDeformLdsWeights + kBiasFloatsArtDeform / 4;
+constexpr int kDeformLdsWeights = kRing * NetArtDeformH::kChunk * 64;                   // f4
+constexpr int kDeformLdsF4 = kDeformLdsWeights + NetArtDeformH::kBiasFloats / 4;
 static_assert(2 * kDeformLdsF4 * 16 <= 160 * 1024, "two workgroups per CU");
 constexpr int64_t kDeformSmallRows = 128 * 256;  // one 128-row workgroup per CU of an MI355X
 
@@ -46,7 +46,7 @@ __global__ __launch_bounds__(GeomH<NCOL>::kThreads, 2) void k_mlp_art_deform_f16
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, j = lane & 15;
 
-  using WP = DmaPipe<G::kThreads, kRing, kChunkArtDeform, Net::kStreamBlocks, Net::kBlocks, kRingLead>;
+  using WP = DmaPipe<G::kThreads, kRing, Net::kChunk, Net::kStreamBlocks, Net::kBlocks, kRingLead>;
   WP p;
   start_chain<Net, G::kThreads>(p, smem, wstream, tid, lane, bias_s, bias_g);
 

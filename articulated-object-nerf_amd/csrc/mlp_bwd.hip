@@ -6,7 +6,7 @@
 // over all samples).
 //
 // Same structure and numerics as the forward (mlp_f16x3.hip / mlp_f16x3_core.hpp): feature-
-// major MFMA tiles, W^T streamed through the LDS-DMA ring (kLayersBwd, packed from the forward
+// major MFMA tiles, W^T streamed through the LDS-DMA ring (kShapeBwd, packed from the forward
 // weights with tr = 1), each finished output pair converted in registers into the next layer's
 // B fragments.  Gradients ride at a power-of-two scale s chosen per call from max|d raw|
 // (|d raw * s| < 2^8: 2^8 of headroom below fp16's 65504 for growth through the chain); the
@@ -185,17 +185,19 @@ static int bwd_pack(const aon_mlp_params* prm, void* packed, aon_stream_t stream
                                    prm->pts_w[7], prm->pts_w[6], prm->pts_w[5],
                                    prm->pts_w[4], prm->pts_w[3], prm->pts_w[2],
                                    prm->pts_w[1]};
-  // row strides of the forward weights (their in-features): rgb 128, views 256 + 27, skip 256 + 63
-  const int ld[kNumLayersBwd] = {128, 283, 256, 256, 256, 319, 256, 256, 256, 256};
+  // the forward layer behind each row; the row stride of its weight is its in-features
+  static_assert(sizeof(kVanillaShape) / sizeof(kVanillaShape[0]) == kNumLayers,
+                "L0..LRGB index kVanillaShape");
+  const int fwd[kNumLayersBwd] = {LRGB, LVIEW, LBOT, L7, L6, L5, L4, L3, L2, L1};
   for (int i = 0; i < kNumLayersBwd; ++i) {
     AON_REQUIRE(w[i], "null layer weight");
     a.w[i] = w[i];
-    a.ldw[i] = ld[i];
+    a.ldw[i] = kVanillaShape[fwd[i]][1];
     a.tr[i] = 1;
   }
   AON_REQUIRE(prm->density_w, "null layer weight");
   a.w2[B_BOTDEN] = prm->density_w;  // segment B of d h7: density_layer^T (1 x 256)
-  a.ldw2[B_BOTDEN] = 256;
+  a.ldw2[B_BOTDEN] = kVanillaShape[LDEN][1];
   a.bf16 = bf16 ? 1 : 0;
   return pack_h(a, packed, (hipStream_t)stream);
 }

@@ -14,7 +14,7 @@
 // the pack's status word (range guard, mlp_f16x3_core.hpp or_ballot; aon_mlp_read_status),
 // and the callers fall back to the fp32 path or refuse the training step.
 //
-// Structure (mlp_layout.hpp kLayersH): feature-major tiles as in mlp.hip; a wave owns 16*NCOL
+// Structure (mlp_layout.hpp kShapeH): feature-major tiles as in mlp.hip; a wave owns 16*NCOL
 // samples; output tiles are produced in pairs (u, u+1) whose accumulators, converted in the
 // epilogue, ARE the next layer's B operand for one 32-feature k-step (lane group g holds rows
 // 4g..4g+3 of both tiles) -- no LDS round trip; the epilogue of pair p overlaps the MFMAs of
@@ -41,9 +41,7 @@ template <typename Net>
 constexpr bool kSigmaOnly = std::is_same<Net, NetVanillaSigmaH>::value;
 // the ring chunks of the prefix: whole chunks, and the last one holds a block the pass reads, so
 // every copy the ring issues is waited for (DmaPipe::begin) before the kernel ends
-static_assert(kStreamBlocksSigma % kChunkH == 0 &&
-                  (kBlocksSigma - 1) / kChunkH == kStreamBlocksSigma / kChunkH - 1,
-              "density-only stream: whole ring chunks, none unused");
+static_assert(NetVanillaSigmaH::kChunk == kChunkH, "density-only stream: cut for this ring");
 
 // The layer sequence of k_mlp_fwd_f16x3 (model.py:95-120)
 template <typename Net, int NCOL, bool STORE, typename T, typename FP>
@@ -88,7 +86,7 @@ __device__ __forceinline__ void vanilla_layers(FP& fp, Frag<2, NCOL>& enc, Frag<
   static_assert(!FOLD || !STORE, "the training forwards keep the bottleneck activation");
   if constexpr (!SIG) {  // (the density-only pass: its stream ends with the density head)
     // bottleneck, no activation (model.py:109) -- the render stream has none: it is folded into
-    // the view layer's weights (mlp_layout.hpp kLayersHFold), which then reads h7 (y) itself
+    // the view layer's weights (mlp_layout.hpp kLayoutHFold), which then reads h7 (y) itself
     if constexpr (!FOLD)
       layer_h<Net, LBOT, false>(fp, y, none, x, bias_l, g, SP::make(tbot, 256, rows, N, g));
 #pragma unroll
@@ -409,12 +407,12 @@ int pack_f16x3(const PackArgs& a, void* packed, hipStream_t stream, bool bf16, b
   PackArgsH h{};
   h.bf16 = bf16 ? 1 : 0;
   if (fold) {
-    // the render stream: kLayersH without the bottleneck, folded into the view layer
+    // the render stream: kShapeH without the bottleneck, folded into the view layer
     fill_net<NetVanillaFoldH>(h);
     h.fold_w = a.w[LBOT];
     h.fold_b = a.b[LBOT];
     h.fold_layer = LF_VIEW;
-    h.fold_k = kLayersH[LBOT].out_real;
+    h.fold_k = NetVanillaH::layer(LBOT).out_real;
   } else {
     fill_net<NetVanillaH>(h);
   }

@@ -26,68 +26,89 @@ struct LayerDesc {
   int bias0;         // first float in the bias table (u*16 floats per layer)
 };
 
+// A network is STATED as a shape table, one LayerShape per layer in consumption order; where
+// each layer sits in the stream is derived (build_layout): blk0 and bias0 are running sums.
+struct LayerShape {
+  int ka, kb, u, len_a, len_b, out_real;  // as in LayerDesc
+};
+template <int N>
+struct Layout {
+  static constexpr int kNumLayers = N;
+  LayerDesc layer[N];
+  int blocks;       // blocks carrying weights
+  int bias_floats;  // 16 per output tile
+};
+// blocks_per_step: 1-KB blocks per (output tile, k-step) -- 1 on the fp32 grid, 2 (hi, lo) on
+// the fp16x3 grid.  DROP >= 0: the table without that row.
+template <int DROP = -1, int N>
+constexpr Layout<(DROP < 0 ? N : N - 1)> build_layout(const LayerShape (&s)[N],
+                                                      int blocks_per_step) {
+  Layout<(DROP < 0 ? N : N - 1)> l{};
+  for (int i = 0, o = 0; i < N; ++i) {
+    if (i == DROP) continue;
+    const LayerShape& r = s[i];
+    l.layer[o++] = {r.ka, r.kb, r.u, r.len_a, r.len_b, r.out_real, l.blocks, l.bias_floats};
+    l.blocks += (r.ka + r.kb) * r.u * blocks_per_step;
+    l.bias_floats += 16 * r.u;
+  }
+  return l;
+}
+constexpr int round_up(int x, int m) { return (x + m - 1) / m * m; }
+// (The built layouts below are plain namespace-scope constexpr objects, one per translation unit,
+// not `inline`: mlp_ws.hip looks layers up per unrolled step, and those lookups fold to the same
+// code as before only from a constant the optimiser sees as local.)
+
 enum { L0 = 0, L1, L2, L3, L4, L5, L6, L7, LDEN, LBOT, LVIEW, LRGB, kNumLayers };
 
 constexpr int kChunk = 16;  // 1-KB blocks per LDS pipeline stage
 
-constexpr LayerDesc kLayers[kNumLayers] = {
-    {4, 0, 16, 63, 0, 256, 0, 0},             // pts_linears.0   256 x 63
-    {16, 0, 16, 256, 0, 256, 64, 256},        // pts_linears.1
-    {16, 0, 16, 256, 0, 256, 320, 512},       // pts_linears.2
-    {16, 0, 16, 256, 0, 256, 576, 768},       // pts_linears.3
-    {16, 0, 16, 256, 0, 256, 832, 1024},      // pts_linears.4
-    {16, 4, 16, 256, 63, 256, 1088, 1280},    // pts_linears.5   256 x (256 + 63)
-    {16, 0, 16, 256, 0, 256, 1408, 1536},     // pts_linears.6
-    {16, 0, 16, 256, 0, 256, 1664, 1792},     // pts_linears.7
-    {16, 0, 1, 256, 0, 1, 1920, 2048},        // density_layer     1 x 256
-    {16, 0, 16, 256, 0, 256, 1936, 2064},     // bottleneck_layer 256 x 256
-    {16, 2, 8, 256, 27, 128, 2192, 2320},     // views_linear.0  128 x (256 + 27)
-    {8, 0, 1, 128, 0, 3, 2336, 2448},         // rgb_layer         3 x 128
+// the exact-fp32 kernel (mlp.hip): ka/kb count 16-feature tiles
+constexpr LayerShape kShape32[kNumLayers] = {
+    {4, 0, 16, 63, 0, 256},     // pts_linears.0   256 x 63
+    {16, 0, 16, 256, 0, 256},   // pts_linears.1
+    {16, 0, 16, 256, 0, 256},   // pts_linears.2
+    {16, 0, 16, 256, 0, 256},   // pts_linears.3
+    {16, 0, 16, 256, 0, 256},   // pts_linears.4
+    {16, 4, 16, 256, 63, 256},  // pts_linears.5   256 x (256 + 63)
+    {16, 0, 16, 256, 0, 256},   // pts_linears.6
+    {16, 0, 16, 256, 0, 256},   // pts_linears.7
+    {16, 0, 1, 256, 0, 1},      // density_layer     1 x 256
+    {16, 0, 16, 256, 0, 256},   // bottleneck_layer 256 x 256
+    {16, 2, 8, 256, 27, 128},   // views_linear.0  128 x (256 + 27)
+    {8, 0, 1, 128, 0, 3},       // rgb_layer         3 x 128
 };
+constexpr auto kLayout32 = build_layout(kShape32, 1);
 
 // The fp16x3 kernel (mlp_f16x3.hip) walks the SAME block grid with 32-feature k-steps and
 // two 1-KB blocks (hi, lo) per (u, k-step): ka/kb count 32-feature k-steps, and segment B
 // (enc / enc_dir, computed in-register) uses the natural feature order.
-constexpr LayerDesc kLayersH[kNumLayers] = {
-    {0, 2, 16, 0, 63, 256, 0, 0},             // pts_linears.0: enc only (segment B)
-    {8, 0, 16, 256, 0, 256, 64, 256},
-    {8, 0, 16, 256, 0, 256, 320, 512},
-    {8, 0, 16, 256, 0, 256, 576, 768},
-    {8, 0, 16, 256, 0, 256, 832, 1024},
-    {8, 2, 16, 256, 63, 256, 1088, 1280},
-    {8, 0, 16, 256, 0, 256, 1408, 1536},
-    {8, 0, 16, 256, 0, 256, 1664, 1792},
-    {8, 0, 1, 256, 0, 1, 1920, 2048},
-    {8, 0, 16, 256, 0, 256, 1936, 2064},
-    {8, 1, 8, 256, 27, 128, 2192, 2320},
-    {4, 0, 1, 128, 0, 3, 2336, 2448},
+constexpr LayerShape kShapeH[kNumLayers] = {
+    {0, 2, 16, 0, 63, 256},     // pts_linears.0: enc only (segment B)
+    {8, 0, 16, 256, 0, 256},
+    {8, 0, 16, 256, 0, 256},
+    {8, 0, 16, 256, 0, 256},
+    {8, 0, 16, 256, 0, 256},
+    {8, 2, 16, 256, 63, 256},
+    {8, 0, 16, 256, 0, 256},
+    {8, 0, 16, 256, 0, 256},
+    {8, 0, 1, 256, 0, 1},       // density_layer
+    {8, 0, 16, 256, 0, 256},    // bottleneck_layer
+    {8, 1, 8, 256, 27, 128},    // views_linear.0
+    {4, 0, 1, 128, 0, 3},       // rgb_layer
 };
+constexpr auto kLayoutH = build_layout(kShapeH, 2);
 
 // The fp16x3 RENDER stream (inference: aon_mlp_fwd / aon_mlp_fwd_encoded): bottleneck_layer has
 // no activation (model.py:109) and feeds only views_linear.0, so the two linear maps are one --
 //   z_view = (Wv[:, :256] Wb) h7 + Wv[:, 256:] enc_dir + (bv + Wv[:, :256] bb)
-// -- and the stream holds no bottleneck layer: the view layer's segment A is h7 with the folded
+// -- and the stream is kShapeH without LBOT: the view layer's segment A is h7 with the folded
 // 128 x 256 weight, formed by the pack (k_pack_h fold_w).  65,536 of the 593,408 MAC per sample
-// (11%) and 256 of the 2,344 blocks go.  The training forwards keep the unfolded kLayersH stream
+// (11%) and the bottleneck's 256 blocks go.  The training forwards keep the unfolded stream
 // (they store the bottleneck activation for the backward).
 enum { LF_VIEW = LDEN + 1, LF_RGB, kNumLayersFold };
-
-constexpr LayerDesc kLayersHFold[kNumLayersFold] = {
-    {0, 2, 16, 0, 63, 256, 0, 0},             // pts_linears.0: enc only (segment B)
-    {8, 0, 16, 256, 0, 256, 64, 256},
-    {8, 0, 16, 256, 0, 256, 320, 512},
-    {8, 0, 16, 256, 0, 256, 576, 768},
-    {8, 0, 16, 256, 0, 256, 832, 1024},
-    {8, 2, 16, 256, 63, 256, 1088, 1280},
-    {8, 0, 16, 256, 0, 256, 1408, 1536},
-    {8, 0, 16, 256, 0, 256, 1664, 1792},
-    {8, 0, 1, 256, 0, 1, 1920, 2048},         // density_layer
-    {8, 1, 8, 256, 27, 128, 1936, 2064},      // views_linear.0 . [bottleneck_layer | I]: 128 x (256 + 27)
-    {4, 0, 1, 128, 0, 3, 2080, 2192},         // rgb_layer
-};
-constexpr int kBlocksFold = 2088;                                  // kBlocks - 256
-constexpr int kStreamBlocksFold = (kBlocksFold + 63) / 64 * 64;   // 2112
-constexpr int kBiasFloatsFold = 2208;                              // kBiasFloats - 256
+constexpr auto kLayoutHFold = build_layout<LBOT>(kShapeH, 2);
+static_assert(kLayoutHFold.layer[LF_VIEW].len_a == kLayoutH.layer[LBOT].out_real,
+              "the folded view layer reads what the bottleneck read");
 
 // fp16x3 numerics: activations carried at 2^3, weights at 2^6, so the lo parts (x - fp16(x))
 // stay in fp16's normal range unscaled and hi*hi, hi*lo, lo*hi share ONE fp32 accumulator at
@@ -96,10 +117,11 @@ constexpr int kBiasFloatsFold = 2208;                              // kBiasFloat
 constexpr float kActS = 8.0f;
 constexpr float kWS = 64.0f;
 
-constexpr int kBlocks = 2344;                                     // sum of (ka+kb)*u
-constexpr int kStreamBlocks = (kBlocks + 63) / 64 * 64;          // 2368: whole chunks of 16/32/64
-constexpr int kNumChunks = kStreamBlocks / kChunk;                // 148
-constexpr int kBiasFloats = 2464;
+// the fp32 stream: whole chunks of 16/32/64
+constexpr int kBlocks = kLayout32.blocks;
+constexpr int kStreamBlocks = round_up(kBlocks, 64);
+constexpr int kNumChunks = kStreamBlocks / kChunk;
+constexpr int kBiasFloats = kLayout32.bias_floats;
 constexpr size_t kStreamBytesF32 = (size_t)kStreamBlocks * 1024;
 // every packed buffer ends in a 16-B status block (word 0: the fp16x3 range guard,
 // mlp_f16x3_core.hpp range_report; zeroed by the pack, read by aon_mlp_status)
@@ -107,23 +129,18 @@ constexpr size_t kStatusBytes = 16;
 constexpr size_t kPackedBytesF32 = kStreamBytesF32 + kBiasFloats * 4 + kStatusBytes;
 
 constexpr bool layout_ok() {
-  int blk = 0, bias = 0;
-  for (int i = 0; i < kNumLayers; ++i) {
-    const LayerDesc& d = kLayers[i];
-    if (d.blk0 != blk || d.bias0 != bias) return false;
+  for (const LayerDesc& d : kLayout32.layer) {
     if (d.blk0 % kChunk) return false;  // every layer starts on a chunk boundary
     if (!(d.u == 1 || d.u % 4 == 0)) return false;
-    blk += (d.ka + d.kb) * d.u;
-    bias += d.u * 16;
   }
-  return blk == kBlocks && bias == kBiasFloats;
+  return true;
 }
 static_assert(layout_ok(), "inconsistent MLP stream layout");
 
 constexpr bool layout_h_ok() {
   for (int i = 0; i < kNumLayers; ++i) {
-    const LayerDesc& a = kLayers[i];
-    const LayerDesc& h = kLayersH[i];
+    const LayerDesc& a = kLayout32.layer[i];
+    const LayerDesc& h = kLayoutH.layer[i];
     if (a.blk0 != h.blk0 || a.bias0 != h.bias0 || a.u != h.u) return false;
     if ((h.ka + h.kb) * h.u * 2 != (a.ka + a.kb) * a.u) return false;
   }
@@ -135,35 +152,36 @@ static_assert(layout_h_ok(), "fp16x3 layout must share the block grid");
 // fp16x3 path, after latent folding: the latent columns of deformations_linear.0,
 // pts_linears.0 / .5 and views_linear.0 meet the same (1, C) code on every sample, so their
 // products are per-call biases (NeRFMLP.folded_biases) and the stream holds only the
-// per-sample columns.  Same block grid rules as kLayersH; ka/kb in 32-feature k-steps.
+// per-sample columns.  Same block grid rules as kShapeH; ka/kb in 32-feature k-steps.
 enum {
   A_D0 = 0, A_D1, A_D2, A_D3, A_DOUT,
   A_P0, A_P1, A_P2, A_P3, A_P4, A_P5, A_P6, A_P7,
   A_DEN, A_BOT, A_V0, A_V1, A_V2, A_V3, A_RGB, kNumLayersArt
 };
 
-constexpr LayerDesc kLayersArt[kNumLayersArt] = {
-    {0, 1, 8, 0, 3, 128, 0, 0},              // deformations_linear.0  128 x 3 (xyz columns)
-    {4, 0, 8, 128, 0, 128, 16, 128},         // deformations_linear.1
-    {4, 0, 8, 128, 0, 128, 80, 256},         // deformations_linear.2
-    {4, 0, 8, 128, 0, 128, 144, 384},        // deformations_linear.3
-    {4, 0, 1, 128, 0, 3, 208, 512},          // deformation_layer        3 x 128
-    {0, 2, 16, 0, 63, 256, 216, 528},        // pts_linears.0   256 x 63 (enc columns)
-    {8, 0, 16, 256, 0, 256, 280, 784},       // pts_linears.1
-    {8, 0, 16, 256, 0, 256, 536, 1040},      // pts_linears.2
-    {8, 0, 16, 256, 0, 256, 792, 1296},      // pts_linears.3
-    {8, 0, 16, 256, 0, 256, 1048, 1552},     // pts_linears.4
-    {8, 2, 16, 256, 63, 256, 1304, 1808},    // pts_linears.5   256 x (256 + 63)
-    {8, 0, 16, 256, 0, 256, 1624, 2064},     // pts_linears.6
-    {8, 0, 16, 256, 0, 256, 1880, 2320},     // pts_linears.7
-    {8, 0, 1, 256, 0, 1, 2136, 2576},        // density_layer    1 x 256
-    {8, 0, 16, 256, 0, 256, 2152, 2592},     // bottleneck_layer 256 x 256
-    {8, 1, 8, 256, 27, 128, 2408, 2848},     // views_linear.0   128 x (256 + 27)
-    {4, 0, 8, 128, 0, 128, 2552, 2976},      // views_linear.1
-    {4, 0, 8, 128, 0, 128, 2616, 3104},      // views_linear.2
-    {4, 0, 8, 128, 0, 128, 2680, 3232},      // views_linear.3
-    {4, 0, 1, 128, 0, 3, 2744, 3360},        // rgb_layer        3 x 128
+constexpr LayerShape kShapeArt[kNumLayersArt] = {
+    {0, 1, 8, 0, 3, 128},       // deformations_linear.0  128 x 3 (xyz columns)
+    {4, 0, 8, 128, 0, 128},     // deformations_linear.1
+    {4, 0, 8, 128, 0, 128},     // deformations_linear.2
+    {4, 0, 8, 128, 0, 128},     // deformations_linear.3
+    {4, 0, 1, 128, 0, 3},       // deformation_layer        3 x 128
+    {0, 2, 16, 0, 63, 256},     // pts_linears.0   256 x 63 (enc columns)
+    {8, 0, 16, 256, 0, 256},    // pts_linears.1
+    {8, 0, 16, 256, 0, 256},    // pts_linears.2
+    {8, 0, 16, 256, 0, 256},    // pts_linears.3
+    {8, 0, 16, 256, 0, 256},    // pts_linears.4
+    {8, 2, 16, 256, 63, 256},   // pts_linears.5   256 x (256 + 63)
+    {8, 0, 16, 256, 0, 256},    // pts_linears.6
+    {8, 0, 16, 256, 0, 256},    // pts_linears.7
+    {8, 0, 1, 256, 0, 1},       // density_layer    1 x 256
+    {8, 0, 16, 256, 0, 256},    // bottleneck_layer 256 x 256
+    {8, 1, 8, 256, 27, 128},    // views_linear.0   128 x (256 + 27)
+    {4, 0, 8, 128, 0, 128},     // views_linear.1
+    {4, 0, 8, 128, 0, 128},     // views_linear.2
+    {4, 0, 8, 128, 0, 128},     // views_linear.3
+    {4, 0, 1, 128, 0, 3},       // rgb_layer        3 x 128
 };
+constexpr auto kLayoutArt = build_layout(kShapeArt, 2);
 
 // ---- backward chain of the vanilla NeRFMLP (training, model.py:95-120 under autograd): the
 // input gradients dL/dX = dZ W (W^T applied feature-major), last layer first, each masked by
@@ -171,21 +189,22 @@ constexpr LayerDesc kLayersArt[kNumLayersArt] = {
 // layer, columns = its outputs; packed from the forward weights with tr = 1.
 enum { B_RGB = 0, B_VIEW, B_BOTDEN, B_7, B_6, B_5, B_4, B_3, B_2, B_1, kNumLayersBwd };
 
-constexpr LayerDesc kLayersBwd[kNumLayersBwd] = {
-    {0, 1, 8, 0, 3, 128, 0, 0},             // rgb_layer^T: d hv = W_rgb^T d rgb (3 -> 128)
-    {4, 0, 16, 128, 0, 256, 16, 128},       // views_linear.0^T, bottleneck columns only
-    {8, 1, 16, 256, 1, 256, 144, 384},      // [bottleneck^T | density^T]: d h7
-    {8, 0, 16, 256, 0, 256, 432, 640},      // pts_linears.7^T: d h6
-    {8, 0, 16, 256, 0, 256, 688, 896},      // pts_linears.6^T: d h5
-    {8, 0, 16, 256, 0, 256, 944, 1152},     // pts_linears.5^T, h4 columns only (not enc)
-    {8, 0, 16, 256, 0, 256, 1200, 1408},    // pts_linears.4^T: d h3
-    {8, 0, 16, 256, 0, 256, 1456, 1664},    // pts_linears.3^T: d h2
-    {8, 0, 16, 256, 0, 256, 1712, 1920},    // pts_linears.2^T: d h1
-    {8, 0, 16, 256, 0, 256, 1968, 2176},    // pts_linears.1^T: d h0
+constexpr LayerShape kShapeBwd[kNumLayersBwd] = {
+    {0, 1, 8, 0, 3, 128},       // rgb_layer^T: d hv = W_rgb^T d rgb (3 -> 128)
+    {4, 0, 16, 128, 0, 256},    // views_linear.0^T, bottleneck columns only
+    {8, 1, 16, 256, 1, 256},    // [bottleneck^T | density^T]: d h7
+    {8, 0, 16, 256, 0, 256},    // pts_linears.7^T: d h6
+    {8, 0, 16, 256, 0, 256},    // pts_linears.6^T: d h5
+    {8, 0, 16, 256, 0, 256},    // pts_linears.5^T, h4 columns only (not enc)
+    {8, 0, 16, 256, 0, 256},    // pts_linears.4^T: d h3
+    {8, 0, 16, 256, 0, 256},    // pts_linears.3^T: d h2
+    {8, 0, 16, 256, 0, 256},    // pts_linears.2^T: d h1
+    {8, 0, 16, 256, 0, 256},    // pts_linears.1^T: d h0
 };
+constexpr auto kLayoutBwd = build_layout(kShapeBwd, 2);
 
 // ---- backward chain of the articulated NeRFMLP (training, model_autodecoder.py:168-239 under
-// autograd), same conventions as kLayersBwd: the view branch, the bottleneck / density heads,
+// autograd), same conventions as kShapeBwd: the view branch, the bottleneck / density heads,
 // the trunk, the enc columns of pts_linears.5 (the skip) and of pts_linears.0 (256 -> 63: the
 // gradient w.r.t. pos_enc(x'), reduced in registers through pos_enc's backward to dL/dx'), the
 // deformation head and the deformation MLP.  Latent columns carry no per-sample gradient (their
@@ -195,167 +214,89 @@ enum {
   AB_P2, AB_P1, AB_P0E, AB_DL, AB_D3, AB_D2, AB_D1, kNumLayersArtBwd
 };
 
-constexpr LayerDesc kLayersArtBwd[kNumLayersArtBwd] = {
-    {0, 1, 8, 0, 3, 128, 0, 0},             // rgb_layer^T: d hv3 (3 -> 128)
-    {4, 0, 8, 128, 0, 128, 16, 128},        // views_linear.3^T: d hv2
-    {4, 0, 8, 128, 0, 128, 80, 256},        // views_linear.2^T: d hv1
-    {4, 0, 8, 128, 0, 128, 144, 384},       // views_linear.1^T: d hv0
-    {4, 0, 16, 128, 0, 256, 208, 512},      // views_linear.0^T, bottleneck columns: d bottleneck
-    {8, 1, 16, 256, 1, 256, 336, 768},      // [bottleneck^T | density^T]: d h7
-    {8, 0, 16, 256, 0, 256, 624, 1024},     // pts_linears.7^T: d h6
-    {8, 0, 16, 256, 0, 256, 880, 1280},     // pts_linears.6^T: d h5
-    {8, 0, 16, 256, 0, 256, 1136, 1536},    // pts_linears.5^T, h4 columns: d h4
-    {8, 0, 4, 256, 0, 63, 1392, 1792},      // pts_linears.5^T, enc columns: d enc (skip)
-    {8, 0, 16, 256, 0, 256, 1456, 1856},    // pts_linears.4^T: d h3
-    {8, 0, 16, 256, 0, 256, 1712, 2112},    // pts_linears.3^T: d h2
-    {8, 0, 16, 256, 0, 256, 1968, 2368},    // pts_linears.2^T: d h1
-    {8, 0, 16, 256, 0, 256, 2224, 2624},    // pts_linears.1^T: d h0
-    {8, 0, 4, 256, 0, 63, 2480, 2880},      // pts_linears.0^T, enc columns: d enc
-    {0, 1, 8, 0, 3, 128, 2544, 2944},       // deformation_layer^T: d hd3 (3 -> 128)
-    {4, 0, 8, 128, 0, 128, 2560, 3072},     // deformations_linear.3^T: d hd2
-    {4, 0, 8, 128, 0, 128, 2624, 3200},     // deformations_linear.2^T: d hd1
-    {4, 0, 8, 128, 0, 128, 2688, 3328},     // deformations_linear.1^T: d hd0
+constexpr LayerShape kShapeArtBwd[kNumLayersArtBwd] = {
+    {0, 1, 8, 0, 3, 128},       // rgb_layer^T: d hv3 (3 -> 128)
+    {4, 0, 8, 128, 0, 128},     // views_linear.3^T: d hv2
+    {4, 0, 8, 128, 0, 128},     // views_linear.2^T: d hv1
+    {4, 0, 8, 128, 0, 128},     // views_linear.1^T: d hv0
+    {4, 0, 16, 128, 0, 256},    // views_linear.0^T, bottleneck columns: d bottleneck
+    {8, 1, 16, 256, 1, 256},    // [bottleneck^T | density^T]: d h7
+    {8, 0, 16, 256, 0, 256},    // pts_linears.7^T: d h6
+    {8, 0, 16, 256, 0, 256},    // pts_linears.6^T: d h5
+    {8, 0, 16, 256, 0, 256},    // pts_linears.5^T, h4 columns: d h4
+    {8, 0, 4, 256, 0, 63},      // pts_linears.5^T, enc columns: d enc (skip)
+    {8, 0, 16, 256, 0, 256},    // pts_linears.4^T: d h3
+    {8, 0, 16, 256, 0, 256},    // pts_linears.3^T: d h2
+    {8, 0, 16, 256, 0, 256},    // pts_linears.2^T: d h1
+    {8, 0, 16, 256, 0, 256},    // pts_linears.1^T: d h0
+    {8, 0, 4, 256, 0, 63},      // pts_linears.0^T, enc columns: d enc
+    {0, 1, 8, 0, 3, 128},       // deformation_layer^T: d hd3 (3 -> 128)
+    {4, 0, 8, 128, 0, 128},     // deformations_linear.3^T: d hd2
+    {4, 0, 8, 128, 0, 128},     // deformations_linear.2^T: d hd1
+    {4, 0, 8, 128, 0, 128},     // deformations_linear.1^T: d hd0
 };
+constexpr auto kLayoutArtBwd = build_layout(kShapeArtBwd, 2);
 
-// compile-time description of one fp16x3 network: its layer table and stream geometry
-template <const LayerDesc* TABLE, int NLAYERS, int BLOCKS, int STREAM_BLOCKS, int BIAS_FLOATS,
-          bool ZERO_BIAS = false>
+// compile-time description of one fp16x3 network: its built layout and stream geometry
+template <const auto& LAYOUT, bool ZERO_BIAS = false>
 struct NetH {
-  static constexpr const LayerDesc* kTable = TABLE;
   static constexpr bool kZeroBias = ZERO_BIAS;  // the backward chains: an all-zero bias table
-  static constexpr int kNumLayers = NLAYERS;
-  static constexpr int kBlocks = BLOCKS;               // blocks carrying weights
-  static constexpr int kStreamBlocks = STREAM_BLOCKS;  // padded to whole LDS chunks
-  static constexpr int kBiasFloats = BIAS_FLOATS;
-  static constexpr size_t kStreamBytes = (size_t)STREAM_BLOCKS * 1024;
-  static constexpr size_t kPackedBytes = kStreamBytes + (size_t)BIAS_FLOATS * 4 + kStatusBytes;
-  static constexpr LayerDesc layer(int i) { return TABLE[i]; }
+  static constexpr int kNumLayers = LAYOUT.kNumLayers;
+  static constexpr int kBlocks = LAYOUT.blocks;                  // blocks carrying weights
+  static constexpr int kStreamBlocks = round_up(kBlocks, 64);    // padded to whole LDS chunks
+  static constexpr int kBiasFloats = LAYOUT.bias_floats;
+  static constexpr size_t kStreamBytes = (size_t)kStreamBlocks * 1024;
+  static constexpr size_t kPackedBytes = kStreamBytes + (size_t)kBiasFloats * 4 + kStatusBytes;
+  static constexpr LayerDesc layer(int i) { return LAYOUT.layer[i]; }
   static constexpr bool ok() {
-    int blk = 0, bias = 0;
-    for (int i = 0; i < NLAYERS; ++i) {
-      const LayerDesc d = TABLE[i];
-      if (d.blk0 != blk || d.bias0 != bias || d.blk0 % 2) return false;
+    for (const LayerDesc& d : LAYOUT.layer) {
+      if (d.blk0 % 2) return false;  // a (hi, lo) pair never straddles a chunk
       if (!(d.u == 1 || d.u % 2 == 0)) return false;
       if (d.len_a > 32 * d.ka || d.len_b > 32 * d.kb || d.out_real > 16 * d.u) return false;
-      blk += (d.ka + d.kb) * d.u * 2;
-      bias += d.u * 16;
     }
-    return blk == BLOCKS && bias == BIAS_FLOATS && STREAM_BLOCKS >= BLOCKS &&
-           STREAM_BLOCKS % 64 == 0;
+    return kStreamBlocks % 64 == 0;
   }
 };
 
-using NetVanillaH = NetH<kLayersH, kNumLayers, kBlocks, kStreamBlocks, kBiasFloats>;
-using NetVanillaFoldH =
-    NetH<kLayersHFold, kNumLayersFold, kBlocksFold, kStreamBlocksFold, kBiasFloatsFold>;
-using NetArtH = NetH<kLayersArt, kNumLayersArt, 2752, 2752, 3376>;
-using NetBwdH = NetH<kLayersBwd, kNumLayersBwd, 2224, 2240, 2432, true>;
-using NetArtBwdH = NetH<kLayersArtBwd, kNumLayersArtBwd, 2752, 2752, 3456, true>;
-static_assert(NetVanillaH::ok(), "inconsistent vanilla fp16x3 layout");
-static_assert(NetVanillaFoldH::ok(), "inconsistent folded vanilla fp16x3 layout");
-// the folded table is kLayersH without LBOT: same trunk and heads, the view layer on h7
-constexpr bool layout_fold_ok() {
-  for (int i = 0; i < kNumLayersFold; ++i) {
-    const LayerDesc& f = kLayersHFold[i];
-    const LayerDesc& h = kLayersH[i < LBOT ? i : i + 1];
-    if (f.ka != h.ka || f.kb != h.kb || f.u != h.u || f.len_a != h.len_a || f.len_b != h.len_b ||
-        f.out_real != h.out_real)
-      return false;
-    if (i < LBOT && (f.blk0 != h.blk0 || f.bias0 != h.bias0)) return false;
-  }
-  const LayerDesc& b = kLayersH[LBOT];
-  return kLayersHFold[LF_VIEW].len_a == b.out_real && kBlocksFold == kBlocks - b.ka * b.u * 2 &&
-         kBiasFloatsFold == kBiasFloats - b.u * 16;
-}
-static_assert(layout_fold_ok(), "folded layout must be kLayersH without the bottleneck");
+using NetVanillaH = NetH<kLayoutH>;
+using NetVanillaFoldH = NetH<kLayoutHFold>;
+using NetArtH = NetH<kLayoutArt>;
+using NetBwdH = NetH<kLayoutBwd, true>;
+using NetArtBwdH = NetH<kLayoutArtBwd, true>;
+static_assert(NetVanillaH::ok() && NetVanillaFoldH::ok() && NetArtH::ok() && NetBwdH::ok() &&
+                  NetArtBwdH::ok(),
+              "inconsistent fp16x3 layout");
 
+// A pass that stops after the first N_LAYERS layers of Net reads a PREFIX of Net's packed stream
+// in place: same buffer, same bias table and status word (behind the WHOLE stream's
+// Net::kStreamBytes, not behind the prefix).  The prefix ends where layer N_LAYERS of the parent
+// begins and rounds up to whole ring chunks of CHUNK blocks (the ring then copies some of that
+// layer's blocks, never read); only the prefix's rows of the bias table are staged in LDS.
+template <typename Net, int N_LAYERS, int CHUNK>
+struct Prefix {
+  static_assert(N_LAYERS >= 1 && N_LAYERS < Net::kNumLayers, "a proper prefix");
+  static constexpr bool kZeroBias = Net::kZeroBias;
+  static constexpr int kNumLayers = N_LAYERS;
+  static constexpr int kChunk = CHUNK;  // 1-KB blocks per ring chunk of the pass
+  static constexpr int kBlocks = Net::layer(N_LAYERS).blk0;
+  static constexpr int kStreamBlocks = round_up(kBlocks, CHUNK);
+  static constexpr int kBiasFloats = Net::layer(N_LAYERS).bias0;
+  static constexpr LayerDesc layer(int i) { return Net::layer(i); }
+  static_assert(kBiasFloats % 4 == 0, "the bias rows are staged as float4");
+  // whole ring chunks inside the parent's buffer, the last one holding a block the pass reads:
+  // every copy the ring issues is waited for (DmaPipe::begin) before the kernel ends
+  static_assert(kStreamBlocks % CHUNK == 0 && kStreamBlocks <= Net::kStreamBlocks &&
+                    (kBlocks - 1) / CHUNK == kStreamBlocks / CHUNK - 1,
+                "prefix stream: whole ring chunks, none unused");
+};
 // The density-only render pass (aon_mlp_fwd_sigma: the coarse level of a render that keeps only
 // the fine level's colour -- its rgb reaches nothing, its sigma the fine level's samples): the
-// trunk and the density head, the first LDEN + 1 layers of kLayersHFold.  The density head is
-// consumed before the view layer, so the pass reads a PREFIX of the packed render stream, in
-// place: same buffer, same bias table and status word (behind the whole stream's
-// NetVanillaFoldH::kStreamBytes, not behind the prefix).  The prefix's 1,936 blocks round up to
-// whole ring chunks of 32 (the ring then copies 16 of the view layer's blocks, never read); only
-// the prefix's rows of the bias table are staged in LDS.
-constexpr int kNumLayersSigma = LDEN + 1;
-constexpr int kBlocksSigma = 1936;
-constexpr int kStreamBlocksSigma = (kBlocksSigma + 31) / 32 * 32;  // 1952
-constexpr int kBiasFloatsSigma = 2064;
-struct NetVanillaSigmaH
-    : NetH<kLayersHFold, kNumLayersSigma, kBlocksSigma, kStreamBlocksSigma, kBiasFloatsSigma> {};
-// the prefix matches the folded stream block for block and bias offset for bias offset: the
-// table is the same array, and the prefix ends where the view layer begins
-constexpr bool layout_sigma_ok() {
-  int blk = 0, bias = 0;
-  for (int i = 0; i < kNumLayersSigma; ++i) {
-    const LayerDesc s = NetVanillaSigmaH::layer(i);
-    const LayerDesc& f = kLayersHFold[i];
-    if (s.ka != f.ka || s.kb != f.kb || s.u != f.u || s.len_a != f.len_a || s.len_b != f.len_b ||
-        s.out_real != f.out_real || s.blk0 != f.blk0 || s.bias0 != f.bias0)
-      return false;
-    if (f.blk0 != blk || f.bias0 != bias) return false;
-    blk += (f.ka + f.kb) * f.u * 2;
-    bias += f.u * 16;
-  }
-  return blk == kBlocksSigma && bias == kBiasFloatsSigma &&
-         kLayersHFold[LF_VIEW].blk0 == kBlocksSigma &&
-         kLayersHFold[LF_VIEW].bias0 == kBiasFloatsSigma &&
-         kBiasFloatsSigma % 4 == 0 && kStreamBlocksSigma >= kBlocksSigma &&
-         kStreamBlocksSigma <= kStreamBlocksFold;
-}
-static_assert(layout_sigma_ok(), "the density-only pass must be a prefix of the folded stream");
-static_assert(NetArtH::ok(), "inconsistent articulated fp16x3 layout");
-
+// trunk and the density head of the render stream, in ring chunks of 32 (mlp_f16x3.hip).
+using NetVanillaSigmaH = Prefix<NetVanillaFoldH, LDEN + 1, 32>;
 // The deformation-only pass (aon_mlp_art_fwd_deform: x' and the deformation of a render's
-// samples, without the trunk and the view branch): deformations_linear.0-3 and deformation_layer,
-// the first A_DOUT + 1 layers of kLayersArt.  The head is consumed before pts_linears.0, so the
-// pass reads a PREFIX of the packed articulated stream in place: same buffer, same bias table
-// and status word (behind the whole stream's NetArtH::kStreamBytes, not behind the prefix).  Its
-// 216 blocks round up to whole ring chunks of 16 (mlp_art_deform.hip's ring; the last chunk then
-// copies 8 of pts_linears.0's blocks, never read); only the prefix's 528 bias rows are staged.
-constexpr int kNumLayersArtDeform = A_DOUT + 1;
-constexpr int kBlocksArtDeform = 216;
-constexpr int kChunkArtDeform = 16;  // 1-KB blocks per ring chunk of the deformation-only pass
-constexpr int kStreamBlocksArtDeform =
-    (kBlocksArtDeform + kChunkArtDeform - 1) / kChunkArtDeform * kChunkArtDeform;  // 224
-constexpr int kBiasFloatsArtDeform = 528;
-struct NetArtDeformH {  // NetH's interface over the prefix (NetH::ok() wants whole 64-block streams)
-  static constexpr const LayerDesc* kTable = kLayersArt;
-  static constexpr bool kZeroBias = false;
-  static constexpr int kNumLayers = kNumLayersArtDeform;
-  static constexpr int kBlocks = kBlocksArtDeform;
-  static constexpr int kStreamBlocks = kStreamBlocksArtDeform;
-  static constexpr int kBiasFloats = kBiasFloatsArtDeform;
-  static constexpr LayerDesc layer(int i) { return kLayersArt[i]; }
-};
-// the prefix matches the articulated stream block for block and bias offset for bias offset: the
-// table is the same array, and the prefix ends where pts_linears.0 begins
-constexpr bool layout_art_deform_ok() {
-  int blk = 0, bias = 0;
-  for (int i = 0; i < kNumLayersArtDeform; ++i) {
-    const LayerDesc s = NetArtDeformH::layer(i);
-    const LayerDesc a = NetArtH::layer(i);
-    if (s.ka != a.ka || s.kb != a.kb || s.u != a.u || s.len_a != a.len_a || s.len_b != a.len_b ||
-        s.out_real != a.out_real || s.blk0 != a.blk0 || s.bias0 != a.bias0)
-      return false;
-    if (a.blk0 != blk || a.bias0 != bias) return false;
-    blk += (a.ka + a.kb) * a.u * 2;
-    bias += a.u * 16;
-  }
-  return blk == kBlocksArtDeform && bias == kBiasFloatsArtDeform &&
-         kLayersArt[A_P0].blk0 == kBlocksArtDeform &&
-         kLayersArt[A_P0].bias0 == kBiasFloatsArtDeform && kBiasFloatsArtDeform % 4 == 0 &&
-         kStreamBlocksArtDeform >= kBlocksArtDeform &&
-         kStreamBlocksArtDeform <= NetArtH::kStreamBlocks &&
-         // whole ring chunks, the last one holding a block the pass reads: every copy the ring
-         // issues is waited for (DmaPipe::begin) before the kernel ends
-         kStreamBlocksArtDeform % kChunkArtDeform == 0 &&
-         (kBlocksArtDeform - 1) / kChunkArtDeform == kStreamBlocksArtDeform / kChunkArtDeform - 1;
-}
-static_assert(layout_art_deform_ok(),
-              "the deformation-only pass must be a prefix of the articulated stream");
-static_assert(NetBwdH::ok(), "inconsistent backward-chain fp16x3 layout");
-static_assert(NetArtBwdH::ok(), "inconsistent articulated backward-chain fp16x3 layout");
+// samples, without the trunk and the view branch): deformations_linear.0-3 and
+// deformation_layer, in ring chunks of 16 (mlp_art_deform.hip's ring).
+using NetArtDeformH = Prefix<NetArtH, A_DOUT + 1, 16>;
 
 // pack-kernel arguments: per-layer torch parameter pointers + the layout table by value
 struct PackArgs {
@@ -426,27 +367,46 @@ struct StreamMap {
     return mode == 0 ? blocks : mode == 1 ? blocks / 2 : (lo >> 1) + (hi - lo) + ((blocks - hi) >> 1);
   }
 };
-// the articulated forward's mixed stream: the deformation MLP (kLayersArt blocks 0..215)
+// the articulated forward's mixed stream: the deformation MLP (the blocks before pts_linears.0)
 // fp16x3 -- x' feeds pos_enc's sin(2^9 x'), where bf16's 2^-9 would cost whole radians -- the
-// trunk, heads and view branch compact bf16: 216 + 1268 = 1484 blocks, 1536 with the padding
-constexpr StreamMap kArtMix{2, 0, 216};
-constexpr int kArtMixUsed = kArtMix.used(2752);
-constexpr int kArtMixStream = (kArtMixUsed + 63) / 64 * 64;
-static_assert(kArtMixUsed == 1484 && kArtMixStream == 1536, "mixed articulated stream");
-static_assert(kArtMix.unmap(kArtMix.map(2750)) == 2750 && kArtMix.unmap(kArtMix.map(214)) == 214 &&
-                  kArtMix.map(216) == 216 && kArtMix.map(218) == 217,
-              "stream map round trip");
+// trunk, heads and view branch compact bf16
+constexpr StreamMap kArtMix{2, 0, NetArtH::layer(A_P0).blk0};
+constexpr int kArtMixUsed = kArtMix.used(NetArtH::kBlocks);
+constexpr int kArtMixStream = round_up(kArtMixUsed, 64);
 // the articulated bf16 mode's view-branch stream (train_art.BF16_VIEW): the deformation MLP, the
-// trunk, density and bottleneck fp16x3 (blocks 0..2407 -- everything the deformation gradients
-// are ill-conditioned in), views_linear.0-3 and rgb_layer compact bf16: 2408 + 172 = 2580 blocks
-constexpr StreamMap kArtMixV{2, 0, 2408};
-constexpr int kArtMixVUsed = kArtMixV.used(2752);
-constexpr int kArtMixVStream = (kArtMixVUsed + 63) / 64 * 64;
-static_assert(kArtMixVUsed == 2580 && kArtMixVStream == 2624 && kArtMixVStream <= 2752,
+// trunk, density and bottleneck fp16x3 (the blocks before views_linear.0 -- everything the
+// deformation gradients are ill-conditioned in), views_linear.0-3 and rgb_layer compact bf16
+constexpr StreamMap kArtMixV{2, 0, NetArtH::layer(A_V0).blk0};
+constexpr int kArtMixVUsed = kArtMixV.used(NetArtH::kBlocks);
+constexpr int kArtMixVStream = round_up(kArtMixVUsed, 64);
+static_assert(kArtMixVStream <= NetArtH::kStreamBlocks, "the mixed streams fit the fp16x3 buffer");
+// round trip: the last pair, the last pair before and the first two hi blocks past the fp16x3 range
+constexpr bool stream_map_ok(StreamMap m, int blocks) {
+  return m.unmap(m.map(blocks - 2)) == blocks - 2 && m.unmap(m.map(m.hi - 2)) == m.hi - 2 &&
+         m.map(m.hi) == m.hi && m.map(m.hi + 2) == m.hi + 1;
+}
+static_assert(stream_map_ok(kArtMix, NetArtH::kBlocks) && stream_map_ok(kArtMixV, NetArtH::kBlocks),
+              "stream map round trip");
+
+// ---- the packed sizes are visible through the C ABI (aon_*_packed_bytes; packs live in
+// checkpointed buffers): the derived totals, pinned.  The only literals of this file.
+template <typename Net>
+constexpr bool net_is(int blocks, int stream_blocks, int bias_floats) {
+  return Net::kBlocks == blocks && Net::kStreamBlocks == stream_blocks &&
+         Net::kBiasFloats == bias_floats;
+}
+static_assert(kBlocks == 2344 && kStreamBlocks == 2368 && kBiasFloats == 2464, "fp32 stream");
+static_assert(net_is<NetVanillaH>(2344, 2368, 2464), "unfolded vanilla stream");
+static_assert(net_is<NetVanillaFoldH>(2088, 2112, 2208), "folded render stream");
+static_assert(net_is<NetVanillaSigmaH>(1936, 1952, 2064), "density-only prefix");
+static_assert(net_is<NetArtH>(2752, 2752, 3376), "articulated stream");
+static_assert(net_is<NetBwdH>(2224, 2240, 2432), "vanilla backward stream");
+static_assert(net_is<NetArtBwdH>(2752, 2752, 3456), "articulated backward stream");
+static_assert(net_is<NetArtDeformH>(216, 224, 528), "deformation-only prefix");
+static_assert(kArtMix.hi == 216 && kArtMixUsed == 1484 && kArtMixStream == 1536,
+              "mixed articulated stream");
+static_assert(kArtMixV.hi == 2408 && kArtMixVUsed == 2580 && kArtMixVStream == 2624,
               "view-branch mixed articulated stream");
-static_assert(kLayersArt[A_V0].blk0 == kArtMixV.hi && kArtMixV.map(2408) == 2408 &&
-                  kArtMixV.unmap(kArtMixV.map(2750)) == 2750,
-              "view-branch stream map");
 
 // Training forward of the fused kernel (launch_f16x3_train): every hidden activation goes to
 // HBM for the backward, as the layer-by-layer path keeps them: h (8, N, 256) post-ReLU

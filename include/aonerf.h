@@ -456,7 +456,7 @@ int aon_mlp_art_fwd_train_bf16(const void* packed, const float* rays_o, const fl
  * deformations_linear.i; row-major dxp (N, 3) = dL/dx' (the deformation head's output, through
  * pos_enc's backward) -- the operands of
  * the weight-gradient GEMMs.  packed: aon_mlp_art_bwd_pack of the forward weights (layout
- * kLayersArtBwd); work: >= 4 bytes.  Buffers 16-byte aligned (dxp: 4). */
+ * kShapeArtBwd); work: >= 4 bytes.  Buffers 16-byte aligned (dxp: 4). */
 size_t aon_mlp_art_bwd_packed_bytes(void);
 int aon_mlp_art_bwd_pack(const aon_mlp_art_params* params, void* packed, aon_stream_t stream);
 int aon_mlp_art_bwd(const void* packed, const float* draw, const uint32_t* masks,

@@ -88,19 +88,21 @@ def test_composite_feat_refusals(L):
 
 
 def test_deformation_prefix_of_the_articulated_stream():
-    """The numbers mlp_layout.hpp's static_assert pins (layout_art_deform_ok), restated from the
-    layer table: the deformation MLP is the first 216 blocks and 528 bias rows of the stream."""
+    """The numbers mlp_layout.hpp pins for the deformation-only prefix, restated from the shape
+    table as build_layout sums them: the deformation MLP is the first 216 blocks (224 with the
+    16-block ring's padding) and 528 bias rows of the stream, where pts_linears.0 begins."""
     text = open(os.path.join(ROOT, "articulated-object-nerf_amd", "csrc", "mlp_layout.hpp")).read()
-    body = text[text.index("constexpr LayerDesc kLayersArt[kNumLayersArt]"):]
-    rows = re.findall(r"\{(\d+), (\d+), (\d+), (\d+), (\d+), (\d+), (\d+), (\d+)\}", body)[:6]
+    body = text[text.index("constexpr LayerShape kShapeArt[kNumLayersArt]"):]
+    rows = re.findall(r"\{(\d+), (\d+), (\d+), (\d+), (\d+), (\d+)\}", body)[:5]
+    assert len(rows) == 5
     blk = bias = 0
-    for ka, kb, u, _, _, _, blk0, bias0 in (tuple(map(int, r)) for r in rows[:5]):
-        assert (blk0, bias0) == (blk, bias)
+    for ka, kb, u, _, _, _ in (tuple(map(int, r)) for r in rows):
         blk, bias = blk + (ka + kb) * u * 2, bias + 16 * u
-    assert (blk, bias) == (216, 528) == tuple(map(int, rows[5][6:]))  # where pts_linears.0 begins
-    assert "constexpr int kBlocksArtDeform = 216;" in text
-    assert "constexpr int kBiasFloatsArtDeform = 528;" in text
-    assert "static_assert(layout_art_deform_ok()" in text
+    assert (blk, bias) == (216, 528)
+    assert "using NetArtDeformH = Prefix<NetArtH, A_DOUT + 1, 16>;" in text
+    assert "static_assert(net_is<NetArtDeformH>(216, 224, 528)" in text
+    assert "constexpr StreamMap kArtMix{2, 0, NetArtH::layer(A_P0).blk0};" in text
+    assert "kArtMix.hi == 216" in text
 
 
 def test_canonical_to_rgb():

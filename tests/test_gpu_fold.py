@@ -1,5 +1,5 @@
 """The f16x3 render stream folds bottleneck_layer into views_linear.0 (csrc/mlp_layout.hpp
-kLayersHFold): bottleneck_layer has no activation and feeds only the view layer, so
+kLayoutHFold): bottleneck_layer has no activation and feeds only the view layer, so
 
     z_view = (Wv[:, :256] Wb) h7 + Wv[:, 256:] enc_dir + (bv + Wv[:, :256] bb)
 

@@ -290,19 +290,6 @@ def use_library(path):
     LIB_PATH = path
 
 
-_variants = {}
-
-
-def variant(name):
-    """An A/B build of the library beside the release one (lib/variants/libaonerf_<name>.so,
-    e.g. ``make -C csrc variant-ws``): same ABI and packed formats, a different kernel behind
-    some entry points.  Test infrastructure only; the product path always uses lib()."""
-    if name not in _variants:
-        _variants[name] = _load(os.path.join(os.path.dirname(LIB_PATH), "variants",
-                                             f"libaonerf_{name}.so"))
-    return _variants[name]
-
-
 def call(name, *args):
     """Invoke an aon_* entry point and turn a non-zero status into an exception."""
     st = getattr(lib(), name)(*args)

@@ -84,13 +84,7 @@ __host__ __device__ inline float exp_sleef(float d) {  // (built with -ffp-contr
 // than the general fp64 exp (the fine compositor runs at 80 VGPRs).  Arguments below -120 (fp32
 // result 0) are clamped; NaN propagates; x > 0 is outside the domain the callers use (correct
 // to x = 88, where fp32 overflows anyway only through the polynomial's accuracy at |r| <= 0.347).
-#ifndef AON_ALPHA_EXP_DEVICE
-#define AON_ALPHA_EXP_DEVICE 0  // 1: timing-only A/B build -- the device's own expf (not the torch value)
-#endif
 __host__ __device__ inline float exp_cr(float xf) {
-#if AON_ALPHA_EXP_DEVICE
-  return expf(xf);
-#endif
   const double x = xf < -120.0f ? -120.0 : (double)xf;
   const double k = __builtin_rint(x * 1.44269504088896338700e+00);
   double r = __builtin_fma(-k, 6.93147180369123816490e-01, x);
@@ -172,9 +166,6 @@ __device__ __forceinline__ float cos_cr(float x) {
   return static_cast<float>(__ocml_cos_f64(static_cast<double>(x)));
 }
 
-#ifndef AON_POS_ENC_NOSIN
-#define AON_POS_ENC_NOSIN 0
-#endif
 // fp32(0.5 * pi) as torch adds it to an fp32 tensor (reference helper.py:139)
 constexpr float kHalfPi = 1.57079637050628662109375f;
 
@@ -215,12 +206,7 @@ __device__ __forceinline__ float pos_enc_feature_fast(float x0, float x1, float 
   const float xc = c == 0 ? x0 : (c == 1 ? x1 : x2);
   const float xb = xc * __builtin_ldexpf(1.0f, min_deg + d);
   const float arg = cosine ? __fadd_rn(xb, kHalfPi) : xb;
-#if AON_POS_ENC_NOSIN  // timing-only A/B build: no sine at all (wrong values; bounds its cost)
-  (void)fast;
-  return arg;
-#else
   return fast ? sincos_cr(arg, 0) : sin_cr(arg);
-#endif
 }
 // wave-uniform: every pos_enc argument of this wave's points (|x| 2^(max_deg - 1) + pi/2) is
 // below kSinCrMax

@@ -228,9 +228,7 @@ __global__ __launch_bounds__(THREADS, AON_GEMM_BF_OCC) void k_gemm_bf16_km(Param
   // step kt: tile kt in LDS stage kt & 1, set (kt % PFB) free for tile kt + PFB
   auto step = [&](int kt, auto set) {
     constexpr int S = decltype(set)::value;
-#ifndef AON_GEMM_ABL_NOLOAD  // timing-only ablations (wrong results)
     if (kt + PFB < nk) load(kt + PFB, set);
-#endif
     const __bf16* s = smem + (kt & 1) * STAGE_BF;
     bf8 b[4];
 #pragma unroll
@@ -241,18 +239,10 @@ __global__ __launch_bounds__(THREADS, AON_GEMM_BF_OCC) void k_gemm_bf16_km(Param
       const bf8 a = *reinterpret_cast<const bf8*>(s + (wm * 64 + 16 * i + r16) * ROWH + 8 * g);
 #pragma unroll
       for (int j = 0; j < 4; ++j)
-#ifndef AON_GEMM_ABL_NOMFMA
         acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b[j], acc[i][j], 0, 0, 0);
-#else
-        acc[i][j][0] += static_cast<float>(a[0]) * static_cast<float>(b[j][0]);
-#endif
     }
-#ifndef AON_GEMM_ABL_NOSTORE
     if (kt + 1 < nk) store(1 - (kt & 1), std::integral_constant<int, (S + 1) % PFB>{});
-#endif
-#ifndef AON_GEMM_ABL_NOSYNC
     __syncthreads();
-#endif
   };
   // prologue: tiles 0 .. PFB-1 in flight, tile 0 published
   static_for<0, PFB>([&](auto set) {

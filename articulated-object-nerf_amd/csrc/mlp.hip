@@ -274,7 +274,7 @@ extern "C" int aon_mlp_read_status(const void* packed, size_t packed_bytes, uint
 }
 
 // samples per wave of the fp16x3 render kernel = 16 x AON_F16X3_NCOL (compile-time A/B knob,
-// tools/build_variants.sh; 2 measured 3-5% slower: DESIGN.md §4)
+// `make variant VDEFS=...`; 2 measured 3-5% slower: DESIGN.md §4)
 #ifndef AON_F16X3_NCOL
 #define AON_F16X3_NCOL 1
 #endif
@@ -336,10 +336,6 @@ static int mlp_launch(int mode, const void* packed, int precision, const float* 
   const int64_t N = B * S;
   if (N == 0) return 0;
   AON_REQUIRE(rows_ok(N), "too many rows");
-#if AON_DATAFLOW_WS_BUILD
-  if (precision == AON_PREC_F16X3 && mode == 0)
-    return launch_ws_f16x3(packed, a0, a1, a2, a3, B, S, act, raw, (hipStream_t)stream);
-#endif
   if (precision == AON_PREC_F16X3)
     return launch_f16x3_render(mode == 1, AON_F16X3_NCOL, packed, a0, a1, a2, a3, B, S, act, raw,
                                (hipStream_t)stream);

@@ -306,10 +306,6 @@ static int art_launch(int mode, const void* packed, const float* a0, const float
   const unsigned grid = chain_grid<G>(N);
   const f4* ws = static_cast<const f4*>(packed);
   const float* bias = stream_bias<NetArtH>(packed);
-#if AON_DATAFLOW_WS_BUILD
-  if (mode == 0)
-    return launch_art_ws_f16x3(packed, a0, a1, a2, a3, B, S, act, raw, (hipStream_t)stream);
-#endif
   hipLaunchKernelGGL((mode == 0 ? k_mlp_art_f16x3<0, 1> : k_mlp_art_f16x3<1, 1>), grid, G::kThreads,
                      0, (hipStream_t)stream, ws, bias, a0, a1, a2, a3, B, S, act, raw, TrainStoreArt{});
   return launch_status("aon_mlp_art_fwd");

@@ -116,9 +116,6 @@ __device__ __forceinline__ void vanilla_layers(FP& fp, Frag<2, NCOL>& enc, Frag<
           o[1] = act_rgb(rgb[c][1], act);
           o[2] = act_rgb(rgb[c][2], act);
         }
-#ifdef AON_ABL_NO_RAW_STORE  // timing-only A/B build (fused-pipeline question): no raw store
-        if (__builtin_isnan(o[0] + o[1] + o[2] + o[3]))
-#endif
         *reinterpret_cast<f4*>(raw + 4 * rows[c]) = o;
       }
     }

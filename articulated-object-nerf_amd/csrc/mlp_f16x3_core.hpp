@@ -56,17 +56,9 @@ constexpr float kF16Max = 65504.0f;
 // left to itself hipcc keeps every ballot live until the final OR, and the hundreds of mask
 // pairs spill into VGPR lanes (1,072 v_writelane / v_readlane in the vanilla kernel, -5%)
 #define AON_PIN_OVF(v) asm("" : "+s"(v))
-#ifndef AON_RANGE_GUARD
-#define AON_RANGE_GUARD 1  // 0: timing-only A/B build without the range test
-#endif
 __device__ __forceinline__ void or_ballot(uint64_t& ovf, bool bad) {
-#if AON_RANGE_GUARD
   ovf |= __builtin_amdgcn_ballot_w64(bad);
   AON_PIN_OVF(ovf);
-#else
-  (void)ovf;
-  (void)bad;
-#endif
 }
 __device__ __forceinline__ void range_report(const float* bias_end, uint64_t ovf) {
   if (ovf && (threadIdx.x & 63) == 0) *reinterpret_cast<uint32_t*>(const_cast<float*>(bias_end)) = 1u;
@@ -129,12 +121,6 @@ struct FragPipe {
   __device__ __forceinline__ void fetch_into(int blk_in, f4& h, f4& l) {
     const int blk = map_block(blk_in);
     if (blk >= P::kUsedBlocks) return;
-#ifdef AON_ABLATE_LDS  // timing-only build: reuse the first fragments (no LDS reads, wrong results)
-    if (blk >= 2 * D) {
-      if (blk % P::kChunk == 0) p.begin(blk / P::kChunk);
-      return;
-    }
-#endif
     if (blk % P::kChunk == 0) p.begin(blk / P::kChunk);
     h = p.block(blk);
     if (f16_block(blk_in)) l = p.block(blk + 1);
@@ -285,9 +271,6 @@ constexpr int kTileStride = 256;  // elements between output tiles of one lane
 // on SCC instead of masking EXEC around itself (s_and_saveexec / s_cbranch_execz / s_or per
 // store).
 __device__ __forceinline__ bool keep_row(int64_t row, int64_t N) {
-#ifdef AON_ABL_NO_KEEP  // timing-only A/B build: the training kernels store nothing they keep
-  return false;
-#endif
   const uint64_t t = static_cast<uint64_t>(row & ~int64_t(15));
   const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(t));
   const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(t >> 32));

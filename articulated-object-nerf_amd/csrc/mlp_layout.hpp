@@ -55,8 +55,7 @@ constexpr Layout<(DROP < 0 ? N : N - 1)> build_layout(const LayerShape (&s)[N],
 }
 constexpr int round_up(int x, int m) { return (x + m - 1) / m * m; }
 // (The built layouts below are plain namespace-scope constexpr objects, one per translation unit,
-// not `inline`: mlp_ws.hip looks layers up per unrolled step, and those lookups fold to the same
-// code as before only from a constant the optimiser sees as local.)
+// not `inline`: making them so is a change with its own assembly diff)
 
 enum { L0 = 0, L1, L2, L3, L4, L5, L6, L7, LDEN, LBOT, LVIEW, LRGB, kNumLayers };
 
@@ -517,18 +516,6 @@ int launch_f16x3_sigma(const void* packed, const float* rays_o, const float* ray
 int launch_f16x3_cond(const void* packed, const float* rays_o, const float* rays_d,
                       const float* cond, const float* t, int64_t B, int S, int act, float* raw,
                       hipStream_t stream);
-// the weight-streamed fp16x3 render forward (mlp_ws.hip; MODE 0 inputs, bit-identical to
-// launch_f16x3_render's MODE 0) -- an A/B variant, not in the release library: `make variant-ws`
-// builds lib/variants/libaonerf_ws.so with AON_DATAFLOW_WS_BUILD = 1, whose render forwards
-// (aon_mlp_fwd, aon_mlp_art_fwd) take this dataflow; the release build has no process-global
-// kernel selection and no environment knobs
-#ifndef AON_DATAFLOW_WS_BUILD
-#define AON_DATAFLOW_WS_BUILD 0
-#endif
-int launch_ws_f16x3(const void* packed, const float* a0, const float* a1, const float* a2,
-                    const float* a3, int64_t B, int S, int act, float* raw, hipStream_t stream);
-int launch_art_ws_f16x3(const void* packed, const float* a0, const float* a1, const float* a2,
-                        const float* a3, int64_t B, int S, int act, float* raw, hipStream_t stream);
 
 }  // namespace mlp
 }  // namespace aon

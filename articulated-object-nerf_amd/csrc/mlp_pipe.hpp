@@ -164,9 +164,6 @@ struct DmaPipe {
     for (int c = 0; c < LEAD && c < kNumChunks; ++c) issue(c);
   }
   __device__ __forceinline__ void begin(int c) {
-#ifdef AON_ABLATE_RING  // timing-only build: every chunk reads buffer 0 (wrong results)
-    if (c > 0) return;
-#endif
     // copies issued after chunk c's: chunks c+1 .. min(c+LEAD-1, last)
     const int ahead = (c + LEAD - 1 < kNumChunks - 1 ? c + LEAD - 1 : kNumChunks - 1) - c;
     static_assert((LEAD - 1) * kCopies <= 31, "vmcnt budget");
@@ -179,9 +176,6 @@ struct DmaPipe {
     if (c + LEAD < kNumChunks) issue(c + LEAD);
   }
   __device__ __forceinline__ f4 block(int b) const {
-#ifdef AON_ABLATE_RING
-    return wbuf[(b % kChunk) * 64 + lane];
-#endif
     // ds_read's immediate offset reaches 64 KB: blocks past it read from a second per-lane base
     // (else hipcc materialises every such address with a v_or)
     const int off = ((b / kChunk) % NBUF) * kChunk * 64 + (b % kChunk) * 64;

@@ -264,9 +264,8 @@ int aon_mlp_fwd(const void* packed, int precision, const float* rays_o, const fl
                 aon_stream_t stream);
 
 /* (ABI 9: no process-global state and no environment knobs.  ABI 8's aon_mlp_set_dataflow is
- * gone: the weight-streamed render dataflow, bit-identical and measured at parity, is an A/B
- * variant library, `make -C csrc variant-ws` -> lib/variants/libaonerf_ws.so, whose aon_mlp_fwd
- * and aon_mlp_art_fwd run it.) */
+ * gone, and so is the weight-streamed render dataflow it selected: bit-identical and measured
+ * at parity) */
 
 /* NeRFMLP.forward on pre-encoded inputs: x (B*S, 63), condition (B, 27) -> out (B*S, 4). */
 int aon_mlp_fwd_encoded(const void* packed, int precision, const float* x,

@@ -5,8 +5,9 @@
 #   scripts/ab.sh OUT TOOL [LIB...]
 #
 # LIB: "default" (lib/libaonerf.so) or NAME (lib/variants/libaonerf_NAME.so, built by
-# tools/build_variants.sh); none given = default + every variant.  Each round runs every LIB
-# once, one process each (AONERF_LIB), so box drift hits all of them alike.
+# `make -C articulated-object-nerf_amd/csrc variant NAME=... VFILES=... VDEFS=...`); none given =
+# default + every variant.  Each round runs every LIB once, one process each (AONERF_LIB, which
+# the tools hand to aonerf._lib.use_library()), so box drift hits all of them alike.
 # TOOL:
 #   mlp        tools/prof_mlp.py --precision f16x3 --reps 4   (fused MLP alone; + --dump FILE: raw sha)
 #   march      tools/prof_march.py                            (fused coarse march, median of 20)

@@ -3,7 +3,10 @@ articulated auto-decoder, both forward numerics) on C5's batch with injected uni
 mean step time over 10 steps -- run once per library build (AONERF_LIB=...) and diff the JSON
 lines: a numerics-preserving kernel change must leave every sha unchanged.
 
+    make -C articulated-object-nerf_amd/csrc variant NAME=X VFILES="..." VDEFS="..."
     AONERF_LIB=articulated-object-nerf_amd/lib/variants/libaonerf_X.so python tools/diag/bf16_ab_outputs.py
+
+(AONERF_LIB goes to aonerf._lib.use_library(); scripts/ab.sh OUT bf16-sha interleaves the builds.)
 """
 import hashlib
 import json

@@ -7,11 +7,13 @@ Modules mirror the reference's API surface for the path:
   aonerf.render     <- LitNeRF.render_rays / render_rays_test (models/vanilla_nerf/model.py)
   aonerf.interface  <- models/interface.py (PSNR definitions, image split)
   aonerf.parallel   -- row-band sharding + RCCL frame gather
+  aonerf.geometry   -- density queries on a grid (NeRFMLP.density of either model)
 All compute runs in libaonerf.so (include/aonerf.h); there is no CPU fallback.
 """
 from . import _lib
 
-__all__ = ["helper", "model", "ray_utils", "render", "interface", "parallel", "load_library"]
+__all__ = ["helper", "model", "ray_utils", "render", "interface", "parallel", "geometry",
+           "load_library"]
 
 
 def load_library():

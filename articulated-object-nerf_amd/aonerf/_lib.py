@@ -204,6 +204,8 @@ _SIGNATURES = {
     "aon_mlp_art_fwd_points": (c_int, [vp, vp, vp, c_i64, c_int, c_int, vp, vp]),
     "aon_mlp_art_fwd_deform": (c_int, [vp, vp, vp, vp, c_i64, c_int, vp, vp, vp]),
     "aon_mlp_art_fwd_deform_points": (c_int, [vp, vp, c_i64, vp, vp, vp]),
+    "aon_mlp_art_fwd_sigma": (c_int, [vp, vp, vp, vp, c_i64, c_int, c_int, vp, vp]),
+    "aon_mlp_art_fwd_sigma_points": (c_int, [vp, vp, c_i64, c_int, vp, vp]),
     "aon_composite_feat": (c_int, [vp, vp, c_i64, c_int, c_i64, c_int, vp, vp]),
     "aon_mlp_art_bwd_packed_bytes": (c_size, []),
     "aon_mlp_art_bwd_pack": (c_int, [ctypes.POINTER(AonMlpArtParams), vp, vp]),

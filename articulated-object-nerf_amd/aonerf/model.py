@@ -139,6 +139,25 @@ class NeRFMLP(nn.Module):
                L.ptr(raw), L.stream(t_vals.device))
         return raw
 
+    @torch.no_grad()
+    def density(self, pos, activated=True):
+        """The density field at points pos (..., 3) -> (...): relu(raw) (``activated``,
+        model.py:187: AON_ACT_VANILLA's sigma) or the raw density_layer output.  One density-only
+        launch (aon_mlp_fwd_sigma with rays_o = pos, rays_d = 0, t = 0, S = 1), so f16x3 only: a
+        fp32 model has no such kernel (aon_mlp_fwd's column 3 is its density).  The range guard
+        reports through the pack's status word, as forward_sigma's.  No backward."""
+        if pos.shape[-1] != 3:
+            raise ValueError("density expects (..., 3) points")
+        if self.precision != "f16x3":
+            raise ValueError("density runs the f16x3 density-only kernel; with precision='fp32' "
+                             "take column 3 of forward_rays (aon_mlp_fwd)")
+        lead = tuple(pos.shape[:-1])
+        pos = L.contig(pos.reshape(-1, 3))
+        N = pos.shape[0]
+        raw = self.forward_sigma(pos, torch.zeros_like(pos), torch.zeros((N, 1), device=pos.device),
+                                 act=L.ACT_VANILLA if activated else L.ACT_NONE)
+        return raw[:, 3].view(lead)
+
     def forward(self, x, condition):
         """reference model.py:95-120: x (B, S, 63) encoded points, condition (B, 27)."""
         L.require_gpu(x, condition)

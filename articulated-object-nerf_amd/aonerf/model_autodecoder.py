@@ -177,6 +177,64 @@ class NeRFMLP(nn.Module):
         bufs = _level.LayerBuffers(geo, xyz.shape[0], xyz.device)
         return _level.art_forward(geo, P, fb.__getitem__, xyz, venc, S, bufs)[1]
 
+    # -- the density alone (:196-223): no bottleneck, view branch or rgb head
+    def _sigma_layerwise(self, xyz, latents):
+        """(R, 4) = [0, 0, 0, raw sigma] of the layer-by-layer path: column 3 of _mlp (the
+        density head reads the trunk alone, so any view encoding gives these bits)."""
+        R = xyz.shape[0]
+        venc = torch.zeros((1, (self.deg_view * 2 + 1) * self.input_ch_view), device=xyz.device)
+        raw = self._mlp(xyz, venc, max(R, 1), latents)
+        raw[:, :3] = 0.0
+        return raw
+
+    @torch.no_grad()
+    def forward_sigma(self, rays_o, rays_d, t_vals, latents, act=L.ACT_NONE):
+        """The density-only pass on samples o + t d (aon_mlp_art_fwd_sigma): (B*S, 4) =
+        [0, 0, 0, sigma], column 3 as forward_rays returns it bit for bit; no bottleneck, view
+        branch, rgb head or view encoding runs.  With ``fused`` off: column 3 of the
+        layer-by-layer forward_rays (raw only), zeros in columns 0..2."""
+        L.require_gpu(rays_o, rays_d, t_vals)
+        B, S = t_vals.shape
+        dev = t_vals.device
+        if self._fused_ok():
+            raw = torch.empty((B * S, 4), device=dev)
+            L.call("aon_mlp_art_fwd_sigma", L.ptr(self.packed_weights(latents)),
+                   L.ptr(L.contig(rays_o)), L.ptr(L.contig(rays_d)), L.ptr(L.contig(t_vals)), B, S,
+                   act, L.ptr(raw), L.stream(dev))
+            return raw
+        if act != L.ACT_NONE:
+            raise ValueError("the layer-by-layer path returns raw outputs only")
+        xyz = torch.empty((B * S, 3), device=dev)
+        L.call("aon_cast_rays", L.ptr(L.contig(rays_o)), L.ptr(L.contig(rays_d)),
+               L.ptr(L.contig(t_vals)), B, S, None, 0, L.ptr(xyz), 0, 0, None, L.stream(dev))
+        return self._sigma_layerwise(xyz, latents)
+
+    @torch.no_grad()
+    def density(self, pos, latents, activated=True):
+        """The density field at points pos (..., 3) under these latent codes -> (...):
+        softplus(raw - 1) (``activated``, model_autodecoder.py:323: what the compositor reads) or
+        the raw density_layer output.  One density-only launch (aon_mlp_art_fwd_sigma_points), or
+        layer by layer on aon_gemm when ``fused`` is off -- or when the pass raised the pack's
+        range flag (one sync, skipped under stream capture; RANGE_WARNING).  No backward."""
+        if pos.shape[-1] != 3:
+            raise ValueError("density expects (..., 3) points")
+        L.require_gpu(pos)
+        lead = tuple(pos.shape[:-1])
+        pos = L.contig(pos.reshape(-1, 3))
+        N, dev = pos.shape[0], pos.device
+        if self._fused_ok():
+            buf = self.packed_weights(latents)
+            raw = torch.empty((N, 4), device=dev)
+            L.call("aon_mlp_art_fwd_sigma_points", L.ptr(buf), L.ptr(pos), N,
+                   L.ACT_ARTIC if activated else L.ACT_NONE, L.ptr(raw), L.stream(dev))
+            if torch.cuda.is_current_stream_capturing() or not L.range_overflow([buf]):
+                return raw[:, 3].view(lead)
+            warnings.warn(RANGE_WARNING, RuntimeWarning)
+        sigma = self._sigma_layerwise(pos, latents)[:, 3]
+        if activated:
+            sigma = torch.nn.functional.softplus(sigma - 1.0)
+        return sigma.view(lead)
+
     # -- the deformation MLP alone (:196-205): x' = x + delta(x, shape, articulation)
     @torch.no_grad()
     def _deform_rows(self, latents, *, rays=None, pos=None, packed=None, range_check=True):
@@ -289,7 +347,7 @@ class NeRF_AE_Art(nn.Module):  # noqa: N801 (reference name)
 
     def forward(self, rays, randomized, white_bkgd, near, far, latents, train=True, *,
                 u_coarse=None, u_fine=None, return_weights=False, return_intermediates=False,
-                timers=None, latent_only=False, maps=False):
+                timers=None, latent_only=False, maps=False, fine_only=False):
         """reference model_autodecoder.py:278-337 -> [(comp_rgb, acc, depth)_coarse, (...)_fine]
         (``u_coarse`` / ``u_fine`` inject randomized-mode uniforms; the extras as NeRF.forward;
         ``timers`` (dict) records hip events around each level's MLP / composite launches).
@@ -306,7 +364,16 @@ class NeRF_AE_Art(nn.Module):  # noqa: N801 (reference name)
         weights (helper.py:191-193's nocs hook) -- ``canonical`` (B, 3) = sum w x',
         ``motion`` (B, 3) = sum w delta, ``motion_mag`` (B,) = sum w ||delta|| -- from one
         deformation pass over the fine samples (aon_mlp_art_fwd_deform) and two
-        aon_composite_feat launches; every other output is unchanged."""
+        aon_composite_feat launches; every other output is unchanged.
+
+        ``fine_only`` (inference path, without ``return_weights`` / ``return_intermediates``; as
+        NeRF.forward, and what aonerf.render asks for): the caller keeps only the fine level, so
+        the first element is None and, with both MLPs on the fused path, the coarse MLP runs the
+        density-only kernel (aon_mlp_art_fwd_sigma): no bottleneck, view branch or rgb head for
+        colours that reach nothing.  The fine level is the same, bit for bit -- the coarse level
+        reaches it through its weights alone, which read sigma and t.  An activation out of the
+        fp16x3 range in the coarse VIEW branch alone is then no longer reported (nothing kept
+        read it); the fine level still reports its own."""
         o, d, v = rays["rays_o"], rays["rays_d"], rays["viewdirs"]
         L.require_gpu(o, d, v)
         o, d, v = L.contig(o), L.contig(d), L.contig(v)
@@ -318,12 +385,22 @@ class NeRF_AE_Art(nn.Module):  # noqa: N801 (reference name)
                              "frozen parameters and latent codes")
         run = two_level.train if training else two_level.render
         kw = dict(maps=True) if maps else {}
-        return run(self._spec(latents, latent_only), o, d, v, randomized, white_bkgd, near, far,
-                   u_coarse=u_coarse, u_fine=u_fine, return_weights=return_weights,
+        fine_only = bool(fine_only) and not (training or return_weights or return_intermediates)
+        if fine_only:
+            kw["fine_only"] = True
+        return run(self._spec(latents, latent_only, fine_only), o, d, v, randomized, white_bkgd,
+                   near, far, u_coarse=u_coarse, u_fine=u_fine, return_weights=return_weights,
                    return_intermediates=return_intermediates, timers=timers, **kw)
 
-    def _spec(self, latents, latent_only=False):
+    def _spec(self, latents, latent_only=False, fine_only=False):
         mlps = (self.coarse_mlp, self.fine_mlp)
+
+        def mlp_raw(level, mlp, o, d, v, t_vals, act):
+            # fine_only: the coarse colour reaches nothing -- density only, while both MLPs are on
+            # the fused path (inside the range fallback: the layer-by-layer forward, as before)
+            if fine_only and level == 0 and all(m._fused_ok() for m in mlps):
+                return mlp.forward_sigma(o, d, t_vals, latents, act=act)
+            return mlp.forward_rays(o, d, v, t_vals, latents, act=act)
 
         def train_level(level, mlp, o, d, v, t_vals, white_bkgd, noise, timers):
             from .train_art import render_level
@@ -346,8 +423,7 @@ class NeRF_AE_Art(nn.Module):  # noqa: N801 (reference name)
 
         return SimpleNamespace(
             model=self, train_level=train_level, maps=level_maps,
-            mlp_raw=lambda level, mlp, o, d, v, t_vals, act: mlp.forward_rays(
-                o, d, v, t_vals, latents, act=act),
+            mlp_raw=mlp_raw,
             # model_autodecoder.py:321-323 always in the compositor (AON_ACT_ARTIC)
             acts=lambda noisy: (L.ACT_NONE, L.ACT_ARTIC),
             keep_fine_weights=True, extras_key="raw",

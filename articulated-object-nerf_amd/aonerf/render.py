@@ -31,11 +31,18 @@ def _maps_kw(maps):
     return {"maps": True} if maps else {}
 
 
+def _model_args(white_bkgd, near, far, latents):
+    # the model call's positional arguments: a model with latent codes (NeRF_AE_Art) takes them
+    # after ``far``; None: a vanilla model, or a closure that binds them itself
+    return (False, white_bkgd, near, far) + (() if latents is None else (latents,))
+
+
 def _put_maps(out, i, j, m):
     out[i:j, 5:8], out[i:j, 8:11], out[i:j, 11] = m["canonical"], m["motion"], m["motion_mag"]
 
 
-def _render_box(model, rays, chunk, white_bkgd, box_side_length, cull, timers=None, maps=False):
+def _render_box(model, rays, chunk, white_bkgd, box_side_length, cull, timers=None, maps=False,
+                latents=None):
     """(B, 5) payload [rgb(3), depth, acc] of ``rays`` bounded by the box of side
     ``box_side_length`` around the origin.  The bounds are formed once over all the rays (the
     fill of get_ray_limits depends on the batch), not per chunk.  ``cull``: only the rays that
@@ -50,8 +57,8 @@ def _render_box(model, rays, chunk, white_bkgd, box_side_length, cull, timers=No
         out = torch.empty((B, 12 if maps else 5), device=dev)
         for i, j in _chunks(B, chunk):
             sub = {k: x[i:j] for k, x in rays.items()}
-            fine = model(sub, False, white_bkgd, near[i:j], far[i:j], timers=timers,
-                         fine_only=True, **kw)[1]
+            fine = model(sub, *_model_args(white_bkgd, near[i:j], far[i:j], latents),
+                         timers=timers, fine_only=True, **kw)[1]
             out[i:j, 0:3] = fine[0]
             out[i:j, 3] = fine[2]
             out[i:j, 4] = fine[1]
@@ -69,8 +76,8 @@ def _render_box(model, rays, chunk, white_bkgd, box_side_length, cull, timers=No
     hit = torch.empty((n, 12), device=dev) if maps else None  # columns 5.. : the hit rays' maps
     for i, j in _chunks(n, chunk):
         sub = {k: c[k][i:j] for k in ("rays_o", "rays_d", "viewdirs")}
-        fine = model(sub, False, white_bkgd, c["near"][i:j], c["far"][i:j], timers=timers,
-                     fine_only=True, **kw)[1]
+        fine = model(sub, *_model_args(white_bkgd, c["near"][i:j], c["far"][i:j], latents),
+                     timers=timers, fine_only=True, **kw)[1]
         comp[i:j], acc[i:j], depth[i:j] = fine[0], fine[1], fine[2]
         if maps:
             _put_maps(hit, i, j, fine[-1])
@@ -85,13 +92,17 @@ def _render_box(model, rays, chunk, white_bkgd, box_side_length, cull, timers=No
 
 @torch.no_grad()
 def render_rays(model, batch, chunk, white_bkgd, near, far, box_side_length=None, cull=True,
-                maps=False):
+                maps=False, latents=None):
     """LitNeRF.render_rays (model.py:295-321): fine-level comp_rgb/acc/depth over all rays and
     psnr_legacy against batch['target'] (returned as 'psnr' instead of being logged).
 
     ``maps`` (a model with a deformation field: NeRF_AE_Art.forward(maps=True)): also
     'canonical' (B, 3), 'motion' (B, 3) and 'motion_mag' (B,), concatenated over the chunks like
     comp_rgb; zero on a ray that box culling dropped.
+
+    ``latents`` (NeRF_AE_Art: the dict of latent codes): passed to the model after ``far``, so
+    the articulated model renders without a closure and gets ``fine_only=True`` -- its coarse
+    level then runs the density-only pass.  None: the model is called as before.
 
     ``box_side_length`` (default None: ``near`` / ``far`` as given): bound every ray by the box
     of that side around the origin instead (helper.get_ray_limits; ``near`` / ``far`` are then
@@ -101,7 +112,8 @@ def render_rays(model, batch, chunk, white_bkgd, near, far, box_side_length=None
     B = batch["rays_o"].shape[0]
     if box_side_length is not None:
         rays = {k: batch[k] for k in ("rays_o", "rays_d", "viewdirs")}
-        p = _render_box(model, rays, chunk, white_bkgd, box_side_length, cull, maps=maps)
+        p = _render_box(model, rays, chunk, white_bkgd, box_side_length, cull, maps=maps,
+                        latents=latents)
         out = {"comp_rgb": p[:, 0:3].contiguous(), "acc": p[:, 4].contiguous(),
                "depth": p[:, 3].contiguous()}
         if maps:
@@ -113,7 +125,8 @@ def render_rays(model, batch, chunk, white_bkgd, near, far, box_side_length=None
     ret = defaultdict(list)
     for i, j in _chunks(B, chunk):
         sub = {k: batch[k][i:j] for k in ("rays_o", "rays_d", "viewdirs")}
-        fine = model(sub, False, white_bkgd, near, far, fine_only=True, **_maps_kw(maps))[1]
+        fine = model(sub, *_model_args(white_bkgd, near, far, latents), fine_only=True,
+                     **_maps_kw(maps))[1]
         ret["comp_rgb"].append(fine[0])
         ret["acc"].append(fine[1])
         ret["depth"].append(fine[2])
@@ -126,10 +139,11 @@ def render_rays(model, batch, chunk, white_bkgd, near, far, box_side_length=None
 
 
 @torch.no_grad()
-def render_rays_test(model, batch, chunk, white_bkgd, near, far):
-    """LitNeRF.render_rays_test (model.py:323-348) -> {target, instance_mask, rgb}."""
+def render_rays_test(model, batch, chunk, white_bkgd, near, far, latents=None):
+    """LitNeRF.render_rays_test (model.py:323-348) -> {target, instance_mask, rgb}
+    (``latents``: as render_rays)."""
     out = render_rays(model, {k: v for k, v in batch.items() if k != "target"}, chunk, white_bkgd,
-                      near, far)
+                      near, far, latents=latents)
     test_output = {"rgb": out["comp_rgb"]}
     for k in ("target", "instance_mask"):
         if k in batch:
@@ -139,21 +153,23 @@ def render_rays_test(model, batch, chunk, white_bkgd, near, far):
 
 @torch.no_grad()
 def render_frame(model, c2w, H, W, focal, near=2.0, far=6.0, white_bkgd=True, p0=0, n=None,
-                 chunk=None, timers=None, box_side_length=None, cull=True, maps=False):
+                 chunk=None, timers=None, box_side_length=None, cull=True, maps=False,
+                 latents=None):
     """Fused ray generation + two-level render of pixels [p0, p0+n) of an H x W frame.
     Returns (n, 5) = [rgb(3), depth, acc] per pixel (the payload of the frame gather).
     ``box_side_length`` / ``cull``: as render_rays (the bounds are formed over the n pixels).
     ``maps`` (as render_rays): (n, 12), the payload followed by canonical (3), motion (3) and
-    motion_mag."""
+    motion_mag.  ``latents``: as render_rays."""
     n = H * W - p0 if n is None else n
     rays = frame_rays(c2w, H, W, focal, p0, n)
     if box_side_length is not None:
-        return _render_box(model, rays, chunk, white_bkgd, box_side_length, cull, timers, maps)
+        return _render_box(model, rays, chunk, white_bkgd, box_side_length, cull, timers, maps,
+                           latents)
     out = torch.empty((n, 12 if maps else 5), device=rays["rays_o"].device)
     for i, j in _chunks(n, chunk):
         sub = {k: v[i:j] for k, v in rays.items()}
-        fine = model(sub, False, white_bkgd, near, far, timers=timers, fine_only=True,
-                     **_maps_kw(maps))[1]
+        fine = model(sub, *_model_args(white_bkgd, near, far, latents), timers=timers,
+                     fine_only=True, **_maps_kw(maps))[1]
         out[i:j, 0:3] = fine[0]
         out[i:j, 3] = fine[2]
         out[i:j, 4] = fine[1]

@@ -296,6 +296,14 @@ using NetVanillaSigmaH = Prefix<NetVanillaFoldH, LDEN + 1, 32>;
 // samples, without the trunk and the view branch): deformations_linear.0-3 and
 // deformation_layer, in ring chunks of 16 (mlp_art_deform.hip's ring).
 using NetArtDeformH = Prefix<NetArtH, A_DOUT + 1, 16>;
+// The articulated density-only pass (aon_mlp_art_fwd_sigma: the coarse level of a render that
+// keeps only the fine level, and density queries at points): everything through density_layer
+// -- the deformation MLP and head, the trunk, the density head -- without bottleneck_layer and
+// the view branch, in the chain ring's chunks of 32 (mlp_art_sigma.hip).  Two workgroups per CU
+// are out of reach at any chunk size: the 256-wide trunk's two Frag<8> fragments alone are 128
+// VGPRs, so a SIMD holds 2 waves = one 8-wave workgroup per CU, and at 16-block chunks the ring
+// (48 KB), the prefix's bias rows (10 KB) and the enc stash (32 KB) would still pass 80 KB.
+using NetArtSigmaH = Prefix<NetArtH, A_DEN + 1, 32>;
 
 // pack-kernel arguments: per-layer torch parameter pointers + the layout table by value
 struct PackArgs {
@@ -402,6 +410,7 @@ static_assert(net_is<NetArtH>(2752, 2752, 3376), "articulated stream");
 static_assert(net_is<NetBwdH>(2224, 2240, 2432), "vanilla backward stream");
 static_assert(net_is<NetArtBwdH>(2752, 2752, 3456), "articulated backward stream");
 static_assert(net_is<NetArtDeformH>(216, 224, 528), "deformation-only prefix");
+static_assert(net_is<NetArtSigmaH>(2152, 2176, 2592), "articulated density-only prefix");
 static_assert(kArtMix.hi == 216 && kArtMixUsed == 1484 && kArtMixStream == 1536,
               "mixed articulated stream");
 static_assert(kArtMixV.hi == 2408 && kArtMixVUsed == 2580 && kArtMixVStream == 2624,

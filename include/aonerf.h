@@ -490,6 +490,28 @@ int aon_mlp_art_fwd_deform(const void* packed, const float* rays_o, const float*
 int aon_mlp_art_fwd_deform_points(const void* packed, const float* pos, int64_t N,
                                   float* xp, float* delta, aon_stream_t stream);
 
+/* The articulated density-only pass (model_autodecoder.py:196-223): the deformation MLP, x',
+ * pos_enc(x'), the trunk and density_layer -- a prefix of aon_mlp_art_pack's stream, read in
+ * place -- and no view encoding, bottleneck_layer, views_linear.0-3 or rgb_layer.
+ * out (B*S, 4) = [0, 0, 0, sigma]: column 3 is aon_mlp_art_fwd's column 3 bit for bit (act as
+ * there: AON_ACT_ARTIC gives softplus(raw - 1)), columns 0..2 are 0; rows past B*S are never
+ * written.  For the coarse level of a render that keeps only the fine level (its colour reaches
+ * nothing) and for density queries at points.  packed and out 16-byte aligned; NULL pointers,
+ * B < 0, S < 1 and an unknown act are refused before any launch; B*S == 0 returns 0.  No
+ * allocation, no synchronisation.
+ * Range: the pass reports through the same status word as aon_mlp_art_fwd, for the values it
+ * splits (the sample points, the deformation and trunk activations, pos_enc(x')); an activation
+ * out of range in the view branch alone is not among them -- a render whose coarse level runs
+ * this pass no longer learns of one there (those colours are not computed; the fine level still
+ * reports its own).  aon_mlp_art_pack clears the word: do not re-pack between the kernels of one
+ * render.  (Added since ABI 13, without a version change.) */
+int aon_mlp_art_fwd_sigma(const void* packed, const float* rays_o, const float* rays_d,
+                          const float* t, int64_t B, int S, int act, float* out,
+                          aon_stream_t stream);
+/* The same on given sample points pos (N, 3). */
+int aon_mlp_art_fwd_sigma_points(const void* packed, const float* pos, int64_t N, int act,
+                                 float* out, aon_stream_t stream);
+
 /* ---------------------------------------------------------------- compositing */
 /* volumetric_rendering (helper.py:157-195) with the activations of model.py:186-187.
  * rgb: (B*S) rows of rgb_stride floats (3 = API tensor, 4 = fused raw buffer);

@@ -66,6 +66,16 @@ int main() {
                  "art_fwd_deform_points null pos");
   expect_invalid(aon_mlp_art_fwd_deform_points(p, dummy, -1, dummy, dummy, nullptr),
                  "art_fwd_deform_points N < 0");
+  expect_invalid(aon_mlp_art_fwd_sigma(p, dummy, dummy, dummy, 4, 8, 0, nullptr, nullptr),
+                 "art_fwd_sigma null out");
+  expect_invalid(aon_mlp_art_fwd_sigma(p, dummy, dummy, dummy, 4, 0, 0, dummy, nullptr),
+                 "art_fwd_sigma S = 0");
+  expect_invalid(aon_mlp_art_fwd_sigma(p, dummy, dummy, dummy, 4, 8, 3, dummy, nullptr),
+                 "art_fwd_sigma bad act");
+  expect_invalid(aon_mlp_art_fwd_sigma_points(p, nullptr, 4, 0, dummy, nullptr),
+                 "art_fwd_sigma_points null pos");
+  expect_invalid(aon_mlp_art_fwd_sigma_points(p, dummy, -1, 0, dummy, nullptr),
+                 "art_fwd_sigma_points N < 0");
   expect_invalid(aon_mlp_pack(nullptr, AON_PREC_F16X3, p, nullptr), "mlp_pack null params");
   aon_mlp_params prm;
   std::memset(&prm, 0, sizeof(prm));
